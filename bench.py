@@ -8,16 +8,22 @@ step   : ONE forward + backward of the rasterizer hot path over one synthetic vi
          drop-in Python API (GaussianRasterizer -> autograd backward), inputs resident in HBM.
          Every allocation, zero-fill and the num_rendered host read-back are inside the timed region.
 
-Usage:  python bench.py [--gpus N --steps K --warmup W] [--config cfg3|cfg5|cfg2|cfg1]
+Usage:  python bench.py [--gpus N --steps K --warmup W] [--config cfg3|cfg5|cfg2|cfg1] [--full] [--dump-outputs DIR]
         N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
                 --master-port P bench.py --gpus N --steps K --warmup W
         cfg2 = BASELINE config 2: 1M Gaussians, 1080p, SH degree 3 RGB + mask + depth, FORWARD only, through the
         diff_gaussian_rasterization_depth drop-in; cfg5 = 5M Gaussians, 1600x1063, 64-D, fwd+bwd.
         Defaults: N = 1, K = 100 timed steps, W = 10 warm-up steps behind untimed settling blocks (--settle seconds, see
-        main()); the whole default run, CPU baseline and parity check included, takes about half a minute.
+        main()).
+        A plain run sets up, settles, warms up, times the K steps, writes --dump-outputs and prints the line: `metric`, `value`,
+        `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the workload description; the extra objects below are null.
+        --full adds them (sustained region, distribution blocks, N > 1 exposed communication, per-stage timing + counters +
+        roofline, CPU baseline + parity); with --full the default run takes about half a minute.
+        --dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (image, radii, the gradients;
+        DIR/<name>.npy, float32; a fixed seeded sample of rows / pixels where an array is larger, <= 60 MiB in all).
         --fast-exp / --ref-on-gpu / --dist-single: reporting and testing aids (see their help texts).
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  Extra objects (--full):
   roofline     dominant kernel: algorithmic bytes per launch (SURVEY.md 8(d) formula) / its
                average duration measured live with HIP events on the launch stream; peak 8000 GB/s.
                `stages` lists EVERY stage the same way; a stage whose frac exceeds 1 is flagged
@@ -107,6 +113,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: sustained region, distribution blocks, N > 1 "
+                         "exposed communication, per-stage timing + counters + roofline, CPU baseline + parity (off: those objects are null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step returned to its caller as DIR/<name>.npy (float32; "
+                         "a fixed seeded sample of rows / pixels of the larger arrays, <= 60 MiB in all)")
     ap.add_argument("--config", default="cfg3", help="cfg3 (default, headline) | cfg5 | cfg2 (forward only) | cfg1 | cfg3s / cfg5s (the same "
                                                      "sizes under the second synthetic law, scenes.make_surface_scene)")
     ap.add_argument("--ply", default=None, help="a trained 3DGS point_cloud.ply (scene/gaussian_model.py:271-322) instead of the synthetic "
@@ -125,9 +137,9 @@ def main():
                          "feature gradient and every rank its camera to this directory (.npy)")
     ap.add_argument("--sustained-seconds", type=float, default=2.0,
                     help="after the K timed steps: views/s over at least this many seconds of back-to-back steps with ONE synchronisation at "
-                         "the end (`sustained`; what a 10 000-iteration training run sees; 0: skip)")
+                         "the end (`sustained`; what a 10 000-iteration training run sees; 0: skip); with --full")
     ap.add_argument("--points", type=int, default=None, help="override Gaussian count (debug only; invalidates the metric)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no parity check")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--rs-ag", action="store_true",
                     help="N > 1: exchange the feature gradients as reduce-scatter -> rank-local feature update (plain SGD, lr "
@@ -140,8 +152,8 @@ def main():
                     help="minimum seconds of untimed settling blocks before the W warm-up steps (0 under a profiler: the "
                          "trace would hold thousands of views)")
     ap.add_argument("--dist-blocks", type=int, default=20,
-                    help="untimed blocks of ten steps after the timed region for the median / p10 / p90 of ms per step (0: skip)")
-    ap.add_argument("--cpu-views", type=int, default=3, help="views the CPU baseline is timed over (SURVEY.md 8(d): >= 3)")
+                    help="untimed blocks of ten steps after the timed region for the median / p10 / p90 of ms per step (0: skip); with --full")
+    ap.add_argument("--cpu-views", type=int, default=3, help="with --full: views the CPU baseline is timed over (SURVEY.md 8(d): >= 3)")
     ap.add_argument("--fast-exp", action="store_true",
                     help="run the product in its MI_RAST_FAST_EXP mode (v_exp_f32 instead of expf; noted in "
                          "config.arithmetic -- the headline number is the default mode)")
@@ -169,6 +181,8 @@ def main():
                     help="reporting only, after the timed region: also time oracle/_ref (the reference's own kernels, translated "
                          "test-only by oracle/build_ref.py) on the same workload and GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     import numpy as np
     import torch
@@ -199,7 +213,7 @@ def main():
     # Who takes part in the exchange (config.comm of the JSON line): every rank's device as the driver sees it, gathered over the SAME
     # process group the gradients travel on -- a line whose n_gpus is N then shows N distinct devices (or shows that it does not).
     comm_ranks = None
-    if dist is not None:
+    if dist is not None and args.full:
         pr_ = torch.cuda.get_device_properties(dev)
         ident = {"rank": rank, "local_rank": local_rank, "device_index": dev.index, "name": pr_.name,
                  "uuid": str(getattr(pr_, "uuid", "")) or None,
@@ -335,7 +349,8 @@ def main():
         torch.cuda.synchronize(dev)
 
     # Settling, untimed and before the W warm-up steps: blocks of max(5, W) steps until the blocks of the last second (at least five) all lie
-    # within 5 % of the fastest block seen, for at least 3 s and at most 20 s of wall time.  The FIRST process on a freshly
+    # within 5 % of the fastest block seen, for at least 3 s and at most 20 s of wall time (10 s in a plain run, which must stay within
+    # 30 s of wall time outside its timed and warm-up steps: a settled box often never passes the 5 % test).  The FIRST process on a freshly
     # provisioned box runs erratically for its first seconds: measured on cfg5, blocks of ten steps took
     # 59, 72, 19, 3.5, 57, 34, 3.6, 3.5 ms/step (and a timed region right after that still caught a burst: 6.2 ms/step),
     # while the same command started again on the same box gives 19 (first step: code-object load), 3.55, 3.55 and then
@@ -345,6 +360,7 @@ def main():
     block_ms, block_end = [], []
     nb = max(5, args.warmup)
     t_settle = time.perf_counter()
+    settle_cap = 20.0 if args.full else 10.0
     phase("settling")
     while True:
         barrier()
@@ -360,7 +376,7 @@ def main():
         # 3-ms step are 0.15 s -- too short to call a box settled whose stalls come seconds apart)
         last = [m for m, te in zip(block_ms, block_end) if now - te <= 1.0]
         last = block_ms[-5:] if len(last) < 5 else last
-        settled = ((len(block_ms) >= 5 and max(last) <= 1.05 * min(block_ms) and now - t_settle >= args.settle) or now - t_settle >= 20.0
+        settled = ((len(block_ms) >= 5 and max(last) <= 1.05 * min(block_ms) and now - t_settle >= args.settle) or now - t_settle >= settle_cap
                    or args.settle <= 0)
         if dist is not None:   # every rank must run the same number of steps (each step holds a collective)
             flag = torch.tensor([0 if settled else 1], device=dev, dtype=torch.int32)
@@ -384,12 +400,40 @@ def main():
         elapsed = float(tt.item())
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step holds (forward outputs + the leaves' gradients), before any further step.  Arrays above
+        # 30 MiB are sampled: the same seeded rows (Gaussians) / pixels (all channels) in every run with the same arguments.
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        budget = 30 << 20
+        outs = {"image": state["color"], "radii": state["radii"]}
+        if fwd_only:
+            outs.update(mask=state["mask"], depth=state["depth"])
+        else:
+            outs.update(grad_means3D=means3D.grad, grad_means2D=state["means2D"].grad, grad_colors_precomp=feats.grad,
+                        grad_opacities=opac.grad, grad_scales=scales.grad, grad_rotations=rots.grad)
+        outs = {k: v for k, v in outs.items() if v is not None}   # (a gradient the backward left unset is not returned)
+        per_gauss = [k for k in outs if k not in ("image", "mask", "depth")]
+        row_bytes = sum(4 * outs[k][0].numel() for k in per_gauss)
+        px_bytes = sum(4 * outs[k].shape[0] for k in ("image", "mask", "depth") if k in outs)
+        n_px = H * W
+        sel_rows = (None if P * row_bytes <= budget else
+                    torch.as_tensor(np.sort(np.random.default_rng(20251015).choice(P, budget // row_bytes, replace=False)), device=dev))
+        sel_px = (None if n_px * px_bytes <= budget else
+                  torch.as_tensor(np.sort(np.random.default_rng(20251016).choice(n_px, budget // px_bytes, replace=False)), device=dev))
+        for k, v in outs.items():
+            v = v.detach()
+            if k in per_gauss:
+                v = v if sel_rows is None else v.index_select(0, sel_rows)
+            else:   # (channels, H, W) -> (channels, pixels)
+                v = v.reshape(v.shape[0], n_px)
+                v = v if sel_px is None else v.index_select(1, sel_px)
+            np.save(os.path.join(args.dump_outputs, f"{k}.npy"), v.float().cpu().numpy())
     # Sustained throughput, reporting only: >= --sustained-seconds of steps back to back, bracketed like the timed region.  A
     # 10 000-iteration training run (README.md:82 of the reference) never pauses; the K-step figure above is a burst behind settling
     # blocks with a synchronisation each, and the chip settles a few per cent lower under an uninterrupted load.
     sustained = None
     phase("sustained region")
-    if args.sustained_seconds > 0:
+    if args.full and args.sustained_seconds > 0:
         n_sus = max(args.steps, int(args.sustained_seconds / max(elapsed / args.steps, 1e-5)) + 1)
         if dist is not None:   # every rank the same count
             tn = torch.tensor([n_sus], device=dev, dtype=torch.int64)
@@ -412,7 +456,7 @@ def main():
     # synchronisation per block, max over ranks per block
     dist_blocks = []
     phase("distribution blocks")
-    for _ in range(max(0, args.dist_blocks)):
+    for _ in range(max(0, args.dist_blocks) if args.full else 0):
         barrier()
         tb = time.perf_counter()
         for _ in range(10):
@@ -433,7 +477,7 @@ def main():
     # N > 1: what the exchange costs on the critical path -- the same ranks' step time with the collective skipped (state["solo"],
     # every rank) against the step time with it, ten steps each, max over the ranks
     comm = None
-    if dist is not None:
+    if dist is not None and args.full:
         def _block(n=10):
             barrier()
             tb_ = time.perf_counter()
@@ -493,7 +537,7 @@ def main():
     # the other ranks never join -- they wait for rank 0 in the dump step's all-reduce / in destroy_process_group.  (Until round 4 these
     # steps did start the gradient all-reduce: harmless on the one-rank group of --dist-single, a deadlock with a real second rank.)
     state["solo"] = True
-    if rank == 0:
+    if rank == 0 and args.full:
         _lib.profile_enable(True)
         acc = {k: 0.0 for k in _lib.MI_STAGES}
         nprof = max(3, min(10, args.steps))
@@ -644,7 +688,7 @@ def main():
     # ---- CPU baseline: the oracle on this box's host cores (rank 0, N == 1 only) + parity of the benchmarked run ------
     cpu_baseline = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dist_single:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.dist_single:
         from oracle import saga_oracle as so
         native = so.use_native_build()   # -O3 -march=native, compiled on THIS machine; same results
         if args.cpu_threads > 0:
@@ -836,7 +880,7 @@ def main():
                 (", RCCL all-reduce of (P,C) feature grads" if world > 1 else ""))
         out = {
             "metric": names.get(args.config, f"train views/sec (fwd+bwd), {args.config}"),
-            "value": round(value, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": round(value, 3), "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(ms_per_step, 4), "sustained": sustained, "timing": timing, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": data,
             "config": {"workload": what, "parallelism": f"view-sharded x{world}" + (" rs-ag" if args.rs_ag and world > 1 else ""), "counters": counters,

@@ -160,7 +160,7 @@ def test_bench_reports_both_opt_ins_as_separately_labelled_objects():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--points", "150000", "--no-cpu-baseline",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "4", "--warmup", "2", "--points", "150000", "--no-cpu-baseline",
                           "--settle", "0", "--dist-blocks", "0", "--sustained-seconds", "0", "--features-only-grad", "--frozen-geometry",
                           "--views", "3", "--frozen-passes", "2"], capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -264,7 +264,7 @@ def test_bench_single_rank_rccl_step():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dist-single", "--steps", "4", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--dist-single", "--full", "--steps", "4", "--warmup", "2",
                           "--points", "200000", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -338,7 +338,7 @@ def test_bench_two_ranks_share_the_one_gpu(tmp_path, exchange):
     env = dict(os.environ, MI_BENCH_SHARE_GPU="1", MI_BENCH_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", MI_BENCH_TRACE="1",
                GLOO_SOCKET_IFNAME="lo")   # (the box's hostname need not resolve)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--points", str(Pn),
+           "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "2", "--points", str(Pn),
            "--settle", "0.2", "--dist-blocks", "2", "--sustained-seconds", "0.05", "--no-cpu-baseline", "--dump-grads", str(tmp_path)]
     if exchange == "rs-ag":
         cmd += ["--rs-ag", "--rs-ag-lr", str(lr)]   # (a step large enough to see: gradients are ~1e-6)
@@ -451,7 +451,7 @@ def test_bench_on_a_ply_scene_with_colmap_cameras(tmp_path):
         f.write(struct.pack("<Q", len(poses)))
         for iid, q, t, name in poses:
             f.write(struct.pack("<idddddddi", iid, *q, *t, 1) + name.encode() + b"\x00" + struct.pack("<Q", 0))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--ply", ply, "--cameras", colmap, "--camera-index", "1", "--config", "cfg3",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--ply", ply, "--cameras", colmap, "--camera-index", "1", "--config", "cfg3", "--full",
            "--steps", "3", "--warmup", "1", "--settle", "0", "--dist-blocks", "0", "--sustained-seconds", "0", "--cpu-views", "1"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -6,13 +6,13 @@ import sys
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "gpurun_out", f"lines_{tag}")
-runs = [("cfg3_default", "python bench.py"), ("cfg3", "python bench.py --ref-on-gpu --steps 30"), ("cfg2", "python bench.py --config cfg2"),
-        ("cfg3s", "python bench.py --config cfg3s"), ("cfg5", "python bench.py --config cfg5 --ref-on-gpu"), ("cfg1", "python bench.py --config cfg1"),
-        ("dist", "python bench.py --dist-single --steps 10 --warmup 3"), ("dist_rsag", "python bench.py --dist-single --rs-ag --steps 10 --warmup 3"), ("fastexp", "python bench.py --fast-exp --no-cpu-baseline"),
-        ("frozen", "python bench.py --frozen-geometry --features-only-grad --views 16 --no-cpu-baseline"),
-        ("frozen_cfg5", "python bench.py --config cfg5 --frozen-geometry --features-only-grad --views 8 --no-cpu-baseline")]
+runs = [("cfg3_default", "python bench.py --full"), ("cfg3", "python bench.py --full --ref-on-gpu --steps 30"), ("cfg2", "python bench.py --full --config cfg2"),
+        ("cfg3s", "python bench.py --full --config cfg3s"), ("cfg5", "python bench.py --full --config cfg5 --ref-on-gpu"), ("cfg1", "python bench.py --full --config cfg1"),
+        ("dist", "python bench.py --full --dist-single --steps 10 --warmup 3"), ("dist_rsag", "python bench.py --full --dist-single --rs-ag --steps 10 --warmup 3"), ("fastexp", "python bench.py --full --fast-exp --no-cpu-baseline"),
+        ("frozen", "python bench.py --full --frozen-geometry --features-only-grad --views 16 --no-cpu-baseline"),
+        ("frozen_cfg5", "python bench.py --full --config cfg5 --frozen-geometry --features-only-grad --views 8 --no-cpu-baseline")]
 out = [f"# Bench lines of the final round build ({tag})",
-       "`python bench.py [--config ...]` on 1x MI355X through gpurun (default: 100 timed steps after 10 warm-up steps and the settling blocks); "
+       "`python bench.py --full [--config ...]` on 1x MI355X (default: 100 timed steps after 10 warm-up steps and the settling blocks); "
        "`--ref-on-gpu` adds `reference_on_gpu` (oracle/_ref = the reference's own kernels, hipify-perl at build time, timed on the same workload "
        "and GPU after the timed region).  `timing` = median / p10 / p90 over 20 untimed blocks of ten steps; `roofline.traffic` / `alu` are shown "
        "only when the committed PMC summary carries the stamp of the library being timed (`roofline.library`).", ""]

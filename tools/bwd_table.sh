@@ -9,7 +9,7 @@ CFG=${1:-cfg3}
 for rep in 1 2; do
 for v in pbase pboth; do
 for a in 0 16384 192; do
-  MI_RAST_LIB=$PWD/seganygaussians_amd/libmi_rast_$v.so MI_RAST_ABLATE=$a python bench.py --config $CFG --no-cpu-baseline --steps 40 --warmup 5 --settle 1 --dist-blocks 0 --sustained-seconds 0 2>/dev/null | tail -1 | python -c "
+  MI_RAST_LIB=$PWD/seganygaussians_amd/libmi_rast_$v.so MI_RAST_ABLATE=$a python bench.py --full --config $CFG --no-cpu-baseline --steps 40 --warmup 5 --settle 1 --dist-blocks 0 --sustained-seconds 0 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('bwd_table $CFG variant=$v ablate=$a blend_bwd_ms', d['config']['stages_ms']['blend_bwd'], 'step_ms', d['ms_per_step'])"

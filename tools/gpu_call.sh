@@ -8,7 +8,7 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   tail -15 $out/pytest.log
 fi
 for cfg in ${CFGS:-cfg3 cfg5 cfg2 cfg3s}; do
-  timeout 300 python bench.py --config $cfg --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $out/bench_$cfg.json 2> $out/bench_$cfg.err
+  timeout 300 python bench.py --full --config $cfg --steps 20 --warmup 3 --no-cpu-baseline ${BENCH_ARGS:-} > $out/bench_$cfg.json 2> $out/bench_$cfg.err
   python - <<EOF
 import json
 try:

@@ -5,7 +5,7 @@ out=gpurun_out/${1:-xcd}; mkdir -p $out
 line() { python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d['config']['stages_ms']; print('$1', d['value'], 'views/s  fwd', s['blend_fwd'], 'bwd', s['blend_bwd'], 'ms/step', d['ms_per_step'])"; }
-B="--no-cpu-baseline --steps 30 --warmup 3 --settle 1 --dist-blocks 0 --sustained-seconds 0"
+B="--full --no-cpu-baseline --steps 30 --warmup 3 --settle 1 --dist-blocks 0 --sustained-seconds 0"
 for cfg in cfg3 cfg3s; do
   for rep in 1 2; do
     timeout 200 python bench.py --config $cfg $B 2>$out/err.log | line "$cfg balanced-bwd  "
