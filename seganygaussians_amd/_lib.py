@@ -28,6 +28,8 @@ EXPORTS = [
     "mi_knn_smooth_forward", "mi_knn_smooth_backward",  # include/mi_knn_smooth.h
     "mi_knn_workspace_bytes", "mi_knn_build", "mi_knn_query", "mi_knn_mean_dist2",  # include/mi_knn.h
     "mi_contrastive_forward", "mi_contrastive_backward",  # include/mi_contrastive.h
+    "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
+    "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
 ]
 
 _lib = None
@@ -110,6 +112,16 @@ def load():
     L.mi_contrastive_forward.argtypes = [i, i, i, vp, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
     L.mi_contrastive_backward.restype = i
     L.mi_contrastive_backward.argtypes = [i, i, i, vp, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mi_contrastive_pack_masks.restype = i
+    L.mi_contrastive_pack_masks.argtypes = [i, i, i, vp, vp, vp]
+    L.mi_contrastive_cover.restype = i
+    L.mi_contrastive_cover.argtypes = [i, i, i, vp, vp, f, vp, vp, vp]
+    L.mi_contrastive_targets.restype = i
+    L.mi_contrastive_targets.argtypes = [i, i, i, vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp]
+    L.mi_contrastive_loss_forward.restype = i
+    L.mi_contrastive_loss_forward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mi_contrastive_loss_backward.restype = i
+    L.mi_contrastive_loss_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

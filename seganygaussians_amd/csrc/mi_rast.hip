@@ -31,6 +31,7 @@
 #endif
 #include "common.h"
 #include "contrastive.h"
+#include "contrastive_loss.h"   // the loss itself: SAM-mask targets and the pair loss
 #include "geometry.h"
 
 using namespace mirast;
@@ -812,6 +813,103 @@ int mi_contrastive_backward(int C, int h, int w, const float* rendered, int H, i
         hipLaunchKernelGGL(contrastive_bwd_rays_kernel, dim3(ray_blocks), dim3(CT_THREADS), lds, stream, C, h, w, H, W, S, ray_yx, N, gates, out,
                            ray_feat, inv_len, dL_dout, dL_drendered, dL_dgates);
     }
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
+
+// ---- contrastive loss: SAM-mask targets and the pair loss (mi_contrastive.h, contrastive_loss.h) ------------------------------
+namespace {
+int cl_check_masks(int M, int H, int W)
+{
+    if (M < 1 || M > MI_CONTRASTIVE_LOSS_MAX_MASKS || H < 1 || W < 1)
+        return fail(MI_RAST_ERR_INVALID, "contrastive loss: need 1 <= M <= 1024 masks and H, W >= 1");
+    return MI_RAST_OK;
+}
+int cl_check_loss(int S, int N, int C, int M)
+{
+    if (S < 0 || N < 1 || N > MI_CONTRASTIVE_LOSS_MAX_SCALES || C < 1 || C > 256 || M < 1 || M > MI_CONTRASTIVE_LOSS_MAX_MASKS)
+        return fail(MI_RAST_ERR_INVALID, "contrastive loss: need S >= 0, 1 <= N <= 32, 1 <= C <= 256, 1 <= M <= 1024");
+    if ((size_t)S * S >= ((size_t)1 << 40)) return fail(MI_RAST_ERR_INVALID, "contrastive loss: too many sampled rays");
+    return MI_RAST_OK;
+}
+}  // namespace
+
+int mi_contrastive_pack_masks(int M, int H, int W, const unsigned char* masks, unsigned long long* packed, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = cl_check_masks(M, H, W)) return rc;
+    if (!masks || !packed) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
+    const int Wq = (W + 63) / 64;
+    const size_t words = (size_t)M * H * Wq;
+    hipLaunchKernelGGL(cl_pack_kernel, dim3((unsigned)((words + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, stream, M, H, W, Wq,
+                       (const uint8_t*)masks, (uint64_t*)packed);
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
+int mi_contrastive_cover(int M, int H, int W, const unsigned long long* packed, const float* ray_rand, float rate,
+                         unsigned char* sampled_ray, unsigned long long* acc, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = cl_check_masks(M, H, W)) return rc;
+    if (!packed || !ray_rand || !sampled_ray || !acc) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
+    const int Wq = (W + 63) / 64;
+    const size_t words = (size_t)H * Wq;
+    hipLaunchKernelGGL(cl_cover_kernel, dim3((unsigned)((words + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, stream, M, H, W, Wq,
+                       (const uint64_t*)packed, ray_rand, rate, (uint8_t*)sampled_ray, acc + CL_ACC_AREA);
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
+int mi_contrastive_targets(int M, int H, int W, const unsigned long long* packed, const long long* sort_idx, int S, const int* ray_yx,
+                           int N, const int* scale_si, const int* scale_ub, unsigned long long* gt, float* a, unsigned long long* acc,
+                           void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = cl_check_masks(M, H, W)) return rc;
+    if (int rc = cl_check_loss(S, N, 1, M)) return rc;
+    if (!packed || !sort_idx || !scale_si || !scale_ub || !acc) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
+    if (S == 0) return MI_RAST_OK;
+    if (!ray_yx || !gt || !a) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null ray buffers");
+    const int Wq = (W + 63) / 64, Wd = (M + 63) / 64;
+    hipLaunchKernelGGL(cl_targets_kernel, dim3((unsigned)(((size_t)S * 64 + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, stream,
+                       M, H, Wq, (const uint64_t*)packed, (const int64_t*)sort_idx, S, ray_yx, N, scale_si, scale_ub, Wd, (uint64_t*)gt, a, acc);
+    hipLaunchKernelGGL(cl_classes_kernel, dim3((unsigned)S), dim3(CL_THREADS), 0, stream, S, N, Wd, (const uint64_t*)gt, acc);
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
+int mi_contrastive_loss_forward(int S, int N, int C, int M, const float* feats, const unsigned long long* gt, const float* a,
+                                const unsigned long long* acc, const float* rand, double* partials, float* out_f32, long long* out_i64,
+                                void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = cl_check_loss(S, N, C, M)) return rc;
+    if (!acc || !out_f32 || !out_i64) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
+    if (S > 0 && (!feats || !gt || !a || !rand || !partials)) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null ray buffers");
+    const int Wd = (M + 63) / 64;
+    const size_t lds = (size_t)CL_ROW_STATS * CL_THREADS * sizeof(double) + (size_t)N * CL_THREADS * sizeof(float) + (size_t)N * Wd * sizeof(uint64_t);
+    if (S > 0)
+        hipLaunchKernelGGL(cl_loss_fwd_kernel, dim3((unsigned)S), dim3(CL_THREADS), lds, stream, S, N, C, Wd, feats, (const uint64_t*)gt, a,
+                           acc, rand, partials);
+    hipLaunchKernelGGL(cl_loss_final_kernel, dim3(1), dim3(CL_THREADS), 0, stream, S, N, (const double*)partials, out_f32, out_i64);
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
+int mi_contrastive_loss_backward(int S, int N, int C, int M, const float* feats, const unsigned long long* gt, const float* a,
+                                 const unsigned long long* acc, const float* rand, const long long* out_i64, const float* g_loss,
+                                 float* dL_dfeats, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = cl_check_loss(S, N, C, M)) return rc;
+    if (S == 0) return MI_RAST_OK;
+    if (!feats || !gt || !a || !acc || !rand || !out_i64 || !g_loss || !dL_dfeats) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
+    const int Wd = (M + 63) / 64;
+    const size_t lds = (size_t)N * CL_THREADS * sizeof(float) + (size_t)N * Wd * sizeof(uint64_t);
+    hipLaunchKernelGGL(cl_loss_bwd_kernel, dim3((unsigned)S), dim3(CL_THREADS), lds, stream, S, N, C, Wd, feats, (const uint64_t*)gt, a, acc,
+                       rand, out_i64, g_loss, dL_dfeats);
     HIP_TRY(hipGetLastError());
     return MI_RAST_OK;
 }
