@@ -260,6 +260,10 @@ def contrastive_loss(feats: torch.Tensor, tg: ContrastiveTargets):
     rand = torch.rand((S, S), device=dev, dtype=torch.float32)      # rand_like(sum_0) (:266)
     out_f32 = torch.empty((3,), device=dev, dtype=torch.float32)
     out_i64 = torch.empty((2,), device=dev, dtype=torch.int64)
-    loss = _PairLoss.apply(feats.contiguous(), tg, rand, out_f32, out_i64)
+    feats = feats.contiguous()
+    if feats.data_ptr() % 16:
+        # cl_pair_corr reads rows of C % 4 == 0 channels as float4: a view with a storage offset goes through a fresh buffer
+        feats = feats.clone()
+    loss = _PairLoss.apply(feats, tg, rand, out_f32, out_i64)
     stats = ContrastiveStats(out_f32[1], out_f32[2], out_i64[0], out_i64[1], tg.class_counts)
     return loss, stats

@@ -51,19 +51,25 @@ def _reference_targets(original_masks, mask_scales, upper_bound_scale, num_sampl
             sampled_scales[idx] -= (sampled_scales[idx] - second_big_scale) * torch.rand(1)[0]
         else:
             sampled_scales[idx] -= sampled_scales[idx] * torch.rand(1)[0]
-        if not upper_bound:
-            gt_vec = torch.zeros_like(sam_masks_sampled_ray)
-            gt_vec[:si + 1, :] = sam_masks_sampled_ray[:si + 1, :]
-            for j in range(si, -1, -1):
-                gt_vec[j, :] = torch.logical_and(torch.logical_not(gt_vec[j + 1:, :].any(dim=0)), gt_vec[j, :])
-            gt_vec[si + 1:, :] = sam_masks_sampled_ray[si + 1:, :]
-        else:
-            gt_vec = sam_masks_sampled_ray
+        gt_vec = _reference_gt_vec(sam_masks_sampled_ray, si, upper_bound)
         gt_corr = torch.einsum('nh,nj->hj', gt_vec, gt_vec)
         gt_corr[gt_corr != 0] = 1
         gt_corrs.append(gt_corr)
     gt_corrs = torch.stack(gt_corrs, dim=0)                                                  # :226
     return sampled_ray, sampled_scales, gt_corrs, per_pixel_weight
+
+
+def _reference_gt_vec(sam_masks_sampled_ray, si, upper_bound):
+    """train_contrastive_feature.py:207-218: one scale's gt_vec (M sorted masks, S rays) from the sorted masks at the rays."""
+    if not upper_bound:
+        gt_vec = torch.zeros_like(sam_masks_sampled_ray)
+        gt_vec[:si + 1, :] = sam_masks_sampled_ray[:si + 1, :]
+        for j in range(si, -1, -1):
+            gt_vec[j, :] = torch.logical_and(torch.logical_not(gt_vec[j + 1:, :].any(dim=0)), gt_vec[j, :])
+        gt_vec[si + 1:, :] = sam_masks_sampled_ray[si + 1:, :]
+    else:
+        gt_vec = sam_masks_sampled_ray
+    return gt_vec
 
 
 def _reference_loss(scale_conditioned_features_sam, gt_corrs, per_pixel_weight):
