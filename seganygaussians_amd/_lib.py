@@ -31,6 +31,7 @@ EXPORTS = [
     "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
     "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
 ]
+MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_scales"]   # include/mi_mask_scales.h
 
 _lib = None
 
@@ -122,6 +123,12 @@ def load():
     L.mi_contrastive_loss_forward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.mi_contrastive_loss_backward.restype = i
     L.mi_contrastive_loss_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.mi_mask_scales_workspace_bytes.restype = C.c_size_t
+    L.mi_mask_scales_workspace_bytes.argtypes = [i, i, i]
+    L.mi_mask_erode.restype = i
+    L.mi_mask_erode.argtypes = [i, i, i, vp, i, i, vp, vp]
+    L.mi_mask_scales.restype = i
+    L.mi_mask_scales.argtypes = [i, i, i, vp, vp, C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp]
     _lib = L
     return L
 
