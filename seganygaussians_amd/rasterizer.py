@@ -148,17 +148,23 @@ class GeometryCache:
     they colour the Gaussians), view / projection matrix and camera position, next to the scalar settings.  The reference's
     renderer passes activation OUTPUTS (gaussian_renderer/__init__.py:337-348: pc.get_opacity, get_scaling, get_rotation), new
     tensors per call, so storage identity alone would never hit -- and a freed tensor's address can be handed to another one.  A
-    fingerprint is memoised per tensor OBJECT (weak reference) and version counter: a parameter or camera tensor that is passed
-    again unchanged costs nothing, any in-place change (`means3D.add_(...)`, an optimizer step on a geometry tensor) bumps
-    `_version`, gets a new fingerprint and misses.  Tensors seen for the first time are fingerprinted by one kernel, behind which
-    the calling thread waits for the stream.
+    fingerprint is memoised per tensor OBJECT (weak reference), version counter, storage (weak reference) and data_ptr(): a
+    parameter or camera tensor that is passed again unchanged costs nothing, any in-place change (`means3D.add_(...)`, an optimizer
+    step on a geometry tensor) bumps `_version`, and rebinding (`p.data = new`, which keeps the object and the version) replaces the
+    storage; either gets a new fingerprint and misses.  Writes through `.data` that keep the storage (`p.data.copy_(...)`,
+    `p.data[:] = ...`) change neither and CANNOT be seen: call `clear()` after them.  Tensors seen for the first time are
+    fingerprinted by one kernel, behind which the calling thread waits for the stream.
 
     Bytes kept per view: the geometry buffer (139 bytes per Gaussian), 4 bytes per blend-list entry, 8 bytes per tile, radii (4 bytes
     per Gaussian).  Least recently used views are dropped beyond `max_bytes`.
 
-    The cached buffers are SHARED between the forwards of a view: two backward passes of the same cached view must not run at the
-    same time on different streams (they would share the packed-gradient scratch of the geometry buffer); one after the other --
-    what a training loop does -- is fine.  `debug=True` forwards and the full-list / verify modes of the tests are never cached."""
+    The cached buffers are SHARED between the forwards of a view, the packed-gradient scratch of the geometry buffer included.  Each
+    entry carries an epoch that every hit bumps: the miss forward's pre-zeroed scratch is taken by its backward only while no hit of
+    that view came in between (otherwise the backward zero-fills it itself, as a hit's backward always does).  So any interleaving
+    of forwards and backwards of cached views on one stream -- several renders of a view in one loss, no-grad renders between a
+    forward and its backward, retained graphs -- gives the uncached results (tests/test_geometry_cache_edges.py).  Two backward
+    passes of the same cached view must not run at the same time on different streams.  `debug=True` forwards and the full-list /
+    verify modes of the tests are never cached."""
 
     def __init__(self, max_bytes=64 << 30):
         import collections
@@ -167,7 +173,7 @@ class GeometryCache:
         self.entries = collections.OrderedDict()
         self.bytes = 0
         self.hits = self.misses = 0
-        self._memo = {}          # id(tensor) -> (weakref, _version, fingerprint)
+        self._memo = {}          # id(tensor) -> (weakref, _version, storage weakref, data_ptr, fingerprint)
         self.lock = threading.Lock()
 
     def stats(self):
@@ -183,7 +189,8 @@ class GeometryCache:
             self.hits = self.misses = 0
 
     def fingerprints(self, tensors, dev):
-        """One 64-bit content fingerprint per tensor (None for an absent one); memoised per (tensor object, version)."""
+        """One 64-bit content fingerprint per tensor (None for an absent one); memoised per (tensor object, version, storage,
+        data_ptr).  The caller has checked that every tensor is a float32 GPU tensor."""
         import weakref
         out = [None] * len(tensors)
         todo = []
@@ -191,8 +198,9 @@ class GeometryCache:
             if t is None or t.numel() == 0:
                 continue
             m = self._memo.get(id(t))
-            if m is not None and m[0]() is t and m[1] == t._version:
-                out[k] = m[2]
+            if (m is not None and m[0]() is t and m[1] == t._version and m[2]() is t.untyped_storage()
+                    and m[3] == t.data_ptr()):
+                out[k] = m[4]
             else:
                 todo.append(k)
         for g0 in range(0, len(todo), 8):
@@ -206,7 +214,7 @@ class GeometryCache:
             for k, v in zip(grp, res):
                 t = tensors[k]
                 out[k] = (int(v), tuple(t.shape), str(t.dtype))
-                self._memo[id(t)] = (weakref.ref(t), t._version, out[k])
+                self._memo[id(t)] = (weakref.ref(t), t._version, weakref.ref(t.untyped_storage()), t.data_ptr(), out[k])
         if len(self._memo) > 4096:   # forget tensors that are gone
             self._memo = {i: m for i, m in self._memo.items() if m[0]() is not None}
         return out
@@ -317,7 +325,8 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
     inside the geometry buffer -- stored by the blend kernel beside its own work (include/mi_rast.h: dL_dcolor_next,
     MI_RAST_PREZERO_BWD) instead of by two fill passes in front of the backward.  The tensor is left on the returned geometry
     buffer as `.mi_prezero` (with `.mi_pack_zeroed = True`); hand both to ONE rasterize_gaussians_backward_native call
-    (`prezeroed=`, `pack_zeroed=`).  The dL_dcolors tensor is only made here while it is no larger than the image (P <= H W:
+    (`prezeroed=`, `pack_zeroed=`).  A forward that fills a GeometryCache entry also leaves `.mi_epoch` = (the entry's epoch, its
+    value now): once a hit has bumped it, the geometry buffer's scratch is no longer known to be zero (pass pack_zeroed=False).  The dL_dcolors tensor is only made here while it is no larger than the image (P <= H W:
     the kernel takes the fill while it at most doubles its own stores; a larger one is cheapest as the backward's own
     torch.zeros, as before); prezero="always" makes it regardless (tests: the library then uses a fill command)."""
     ready = _opts.features_ready          # one-shot: consumed by THIS forward whatever happens below (P == 0, an exception)
@@ -354,11 +363,17 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
         cache, ckey = _geometry_cache, None
         if cache is not None and cache.enabled and not debug and not (int(_opts.flags) & _NOCACHE_FLAGS) and not prefiltered:
             colours_from_sh = col_c is None or col_c.numel() == 0
+            # the uncached call's device / dtype checks, in its order and with its messages, before a fingerprint kernel reads data_ptr()
+            for x, name in ((bg_c, "bg"), (m3_c, "means3D"), (sh_c, "sh"), (col_c, "colors_precomp"), (op_c, "opacities"),
+                            (sc_c, "scales"), (rot_c, "rotations"), (cov_c, "cov3D_precomp"), (vm_c, "viewmatrix"),
+                            (pm_c, "projmatrix"), (cp_c, "campos")):
+                _dev_ptr(x, name, dev)
             fps = cache.fingerprints([m3_c, op_c, sc_c, rot_c, cov_c, sh_c if colours_from_sh else None, vm_c, pm_c, cp_c], dev)
             ckey = (dev.index, P, H, W, float(tan_fovx), float(tan_fovy), float(scale_modifier), int(degree), int(M) if colours_from_sh else -1,
                     int(_opts.flags), tuple(fps))
             hit = cache.lookup(ckey)
             if hit is not None:
+                hit["epoch"][0] += 1                 # the miss forward's pre-zeroed scratch is no longer its backward's alone
                 img_t = torch.empty(hit["img_bytes"], dtype=torch.uint8, device=dev)
                 with torch.cuda.device(dev):
                     rc = L.mi_rast_forward_reuse(
@@ -377,7 +392,7 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
                     geom_t.mi_prezero = grad_colors
                     geom_t.mi_pack_zeroed = False    # (the packed-gradient scratch is shared between the forwards of a cached view: its backward fills it)
                 res = (hit["num_rendered"], out_color) + ((out_mask, out_depth) if with_mask_depth else ()) + \
-                      (hit["radii"], geom_t, hit["blend_list"], img_t)
+                      (hit["radii"].clone(), geom_t, hit["blend_list"], img_t)   # (a caller may change its radii in place)
                 return res
         with torch.cuda.device(dev):
             rc = L.mi_rast_forward(
@@ -409,11 +424,13 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
             tiles = ((W + 15) // 16) * ((H + 15) // 16)
             words = img.tensor[ioff["num_rendered"] + 8192:ioff["num_rendered"] + 8192 + 64].clone()
             n_list = int(words.view(torch.int32)[0].item()) if rendered > 0 else 0   # entries the lists hold (lean: <= num_rendered)
-            entry = {"geom": geom.tensor, "num_rendered": rendered, "radii": radii, "img_bytes": int(img.tensor.numel()),
+            entry = {"geom": geom.tensor, "num_rendered": rendered, "radii": radii.clone(), "img_bytes": int(img.tensor.numel()),
                      "blend_list": binning.tensor[:max(4 * n_list, 4)].clone(), "ranges": img.tensor[ioff["ranges"]:ioff["ranges"] + 8 * tiles].clone(),
-                     "words": words, "longest_run": int(L.mi_rast_last_longest_run())}
+                     "words": words, "longest_run": int(L.mi_rast_last_longest_run()), "epoch": [0]}
             entry["bytes"] = sum(int(entry[k].numel()) * entry[k].element_size() for k in ("geom", "blend_list", "ranges", "words", "radii"))
             cache.insert(ckey, entry)
+            if prezero:
+                geom.tensor.mi_epoch = (entry["epoch"], 0)   # the backward takes the zeroed scratch only while no hit came in between
     else:
         out_color = torch.zeros((channels, H, W), dtype=torch.float32, device=dev)
         out_mask = torch.zeros((1, H, W), dtype=torch.float32, device=dev) if with_mask_depth else None
@@ -670,6 +687,7 @@ def _make_plain(channels):
             ctx.mi_flags = getattr(geomBuffer, "mi_flags", 0)
             ctx.mi_prezero = geomBuffer.__dict__.pop("mi_prezero", None)   # one-shot: the first backward takes them
             ctx.mi_pack_zeroed = bool(geomBuffer.__dict__.pop("mi_pack_zeroed", False))
+            ctx.mi_epoch = geomBuffer.__dict__.pop("mi_epoch", None)   # (cache entry epoch, value): a cacheable miss (GeometryCache)
             ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
                                   binningBuffer, imgBuffer)
             ctx.mark_non_differentiable(radii)
@@ -692,6 +710,8 @@ def _make_plain(channels):
 
             prezeroed, ctx.mi_prezero = ctx.mi_prezero, None   # (a second backward through a retained graph fills for itself)
             pack_zeroed, ctx.mi_pack_zeroed = ctx.mi_pack_zeroed, False
+            if pack_zeroed and ctx.mi_epoch is not None and ctx.mi_epoch[0][0] != ctx.mi_epoch[1]:
+                pack_zeroed = False   # a hit of this cached view shares the scratch and may have used it: fill it again
 
             feat_only = _features_only_applies(channels, colors_precomp, ctx.needs_input_grad, rs.debug)
 
