@@ -68,9 +68,10 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_profiling_library(verbose: bool = False) -> str:
-    """The same sources with -DMI_RAST_PROFILING: run-time ablation masks (MI_RAST_ABLATE / MI_RAST_ABLATE_FWD), in-kernel
-    cycle counters, the VALU comparison kernels.  For tools/ only; the product library carries none of it.  Select it with
-    MI_RAST_LIB=<path> (seganygaussians_amd/_lib.py)."""
+    """The same sources with -DMI_RAST_PROFILING: the comparison forward kernels selected by MI_RAST_TILE_FWD (tile-batched
+    bf16x3 / RGB) and MI_RAST_F32_BLEND (f32 FMA chain, the tests' bit-exact reference), and per-wave XCD time stamps in the
+    blend kernels (mi_rast_xcd_stamps, tools/xcd_stamps.py).  For tests and tools/ only; the product library carries none of
+    it.  Select it with MI_RAST_LIB=<path> (seganygaussians_amd/_lib.py)."""
     cmd = [find_hipcc()] + HIPCC_FLAGS + ["-DMI_RAST_PROFILING"] + _hash_flag(["-DMI_RAST_PROFILING"]) + ["-o", PROF_LIB_PATH + ".tmp",
                                           os.path.join(SRC_DIR, "mi_rast.hip")]
     if verbose:

@@ -134,7 +134,6 @@ constexpr uint32_t ID_MASK = (1u << ID_BITS) - 1u;
 constexpr int BIN_MAX_WG = 256;        // workgroups of the count / emit passes (slices of the Gaussians): one per CU, all resident at once
 constexpr int BIN_THREADS = 1024;
 constexpr int BIN_LEAN_WG = 256;       // workgroups of the LEAN count / emit passes (dealt to the bands by load, binning.h: band_plan)
-constexpr int BIN_LEAN_WG_MAX = 1024;  // (upper bound of the profiling build's MI_RAST_LEAN_NWG knob)
 constexpr int BIN_MAX_TILES = 22 * 1024 - 64;  // per launch of the count / emit passes: one LDS counter per tile + 61 KB of hand-off
                                                // arrays must fit in 160 KB; larger images are walked in bands of tile rows
 constexpr int BIN_MAX_TILES_TOTAL = 40 * 1024 - 128;  // tile_ranges_kernel scans all tile totals in one workgroup's LDS
@@ -198,7 +197,7 @@ __global__ void __launch_bounds__(1024) tile_ranges_kernel(int ntiles_all, const
     // run_cap > 0 (images of one segment): the XCD runs of the blend kernels are cut at equal sums of the
     // MODELLED cost of a tile, min(list length, run_cap) + run_fix -- a list is walked until its pixels are opaque, which takes about
     // run_cap entries where the scene is dense, and to its end where it is sparse; what a walk really covers is only known behind the
-    // forward blend (run_bounds_from_walks_kernel) -- the second prefix sum rides on the first, at the granularity of the threads'
+    // forward blend -- the second prefix sum rides on the first, at the granularity of the threads'
     // pieces (registers only); the thread whose piece holds a boundary walks its few tiles.
     // Also left for the per-tile sort: the number of low key bits in which the view's depth keys differ at all (NR_KEY_BITS) --
     // min and max key share every bit above, and so does every key between them.
@@ -376,60 +375,6 @@ __global__ void __launch_bounds__(256) reuse_image_state_kernel(uint32_t ntiles,
         zero_b[t] = 0u;
     }
     if (t < 16u) words[t] = src_words[t];   // {R, longest list, -, key bits, run boundaries}: the 16 words behind the R partial sums
-}
-
-// Run boundaries of the BACKWARD blend from what the forward walked (tile_nsurv: the entries of a tile's list the forward reached
-// before every pixel was opaque -- the tile's cost in both blend kernels; common.h "WORK-balanced runs"), one workgroup, launched
-// behind the forward blend of a view that will be differentiated: scan of (tile_nsurv + XCD_TILE_WEIGHT) over the row-major tile
-// sequence, seven searches for the points of equal weight, the clamp that bounds the backward's grid.  Images above
-// BIN_MAX_TILES_TOTAL tiles keep the equal-count boundaries of the range scan.
-__global__ void __launch_bounds__(1024) run_bounds_from_walks_kernel(int ntiles, const uint32_t* __restrict__ tile_nsurv,
-                                                                      uint32_t* __restrict__ run_bounds)
-{
-    extern __shared__ uint32_t s_w[];   // [ntiles + 1] exclusive prefix of the weights
-    __shared__ uint32_t s_wave2[16];
-    __shared__ uint32_t s_bound2[9];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t n = (uint32_t)ntiles;
-    for (int i = tid; i < ntiles; i += 1024) s_w[i] = tile_nsurv[i] + XCD_TILE_WEIGHT;
-    __syncthreads();
-    const int per = (ntiles + 1023) / 1024;
-    const int i0 = min(ntiles, tid * per), i1 = min(ntiles, i0 + per);
-    uint32_t sum = 0;
-    for (int i = i0; i < i1; i++) {
-        const uint32_t c = s_w[i];
-        s_w[i] = sum;
-        sum += c;
-    }
-    const uint32_t incl = wave_inclusive_scan(sum, lane);
-    if (lane == 63) s_wave2[wave] = incl;
-    __syncthreads();
-    uint32_t woff = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < 16; w++) {
-        const uint32_t c = s_wave2[w];
-        woff += w < wave ? c : 0u;
-        total += c;
-    }
-    const uint32_t base = woff + incl - sum;
-    for (int i = i0; i < i1; i++) s_w[i] += base;
-    if (tid == 0) s_w[ntiles] = total;
-    __syncthreads();
-    if (tid >= 1 && tid <= 7) {   // first tile i with 8 W(i) >= k W_total, W(i) = weight in front of tile i
-        const uint64_t want = (uint64_t)tid * (uint64_t)total;
-        uint32_t lo = 0, hi = n;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (8ull * (uint64_t)s_w[mid] >= want) hi = mid;
-            else lo = mid + 1;
-        }
-        s_bound2[tid] = lo;
-    }
-    __syncthreads();
-    if (tid == 0) {
-        xcd_clamp_runs(s_bound2, n);
-        for (int k = 0; k < 9; k++) run_bounds[k] = s_bound2[k];
-    }
 }
 
 // Everything needed to evaluate a Gaussian at a pixel in ONE 32-byte record (the reference gathers id -> xy -> conic per batch
@@ -668,7 +613,7 @@ __global__ void __launch_bounds__(1024) bin_spans_kernel(int P, const BlendRec* 
                                                          uint32_t* __restrict__ partial, uint32_t* __restrict__ tile_total, const uint2* __restrict__ ranges,
                                                          uint2* __restrict__ entries, uint32_t gx, uint32_t gy_all,
                                                          uint32_t band_h, uint32_t nbands, const int* __restrict__ r_slots,
-                                                         int* __restrict__ host_r, int ablate)
+                                                         int* __restrict__ host_r)
 {
     // COUNT: s_dyn = difference grid [band rows][stride] (ints), then the chunk counter and the waves' hand-off words
     // EMIT : s_dyn = cursors [band tiles], then the same
@@ -800,10 +745,9 @@ __global__ void __launch_bounds__(1024) bin_spans_kernel(int P, const BlendRec* 
             }
         }
         const uint32_t hincl = wave_inclusive_scan_dpp(h);
-        uint32_t rows_total = (uint32_t)__builtin_amdgcn_readlane((int)hincl, 63);
+        const uint32_t rows_total = (uint32_t)__builtin_amdgcn_readlane((int)hincl, 63);
         w_pre[lane] = hincl;
         wave_lds_fence();
-        if MI_ABLATE(1 << 20) rows_total = 0;
         for (uint32_t w0 = 0; w0 < rows_total; w0 += 64) {  // windows of 64 (Gaussian, tile row) items
             const uint32_t k = w0 + (uint32_t)lane;
             uint32_t width = 0;
@@ -851,7 +795,7 @@ __global__ void __launch_bounds__(1024) bin_spans_kernel(int P, const BlendRec* 
                     }
                 }
             }
-            if (EMIT && !MI_ABLATE(1 << 16)) {
+            if (EMIT) {
                 const uint32_t tincl = wave_inclusive_scan_dpp(width);
                 const uint32_t tiles_total = (uint32_t)__builtin_amdgcn_readlane((int)tincl, 63);
                 w_tpre[lane] = tincl;
@@ -867,10 +811,10 @@ __global__ void __launch_bounds__(1024) bin_spans_kernel(int P, const BlendRec* 
                         const uint32_t c = 2u * tx;
                         const uint32_t qmask = (uint32_t)(c - lo0 < n0) | ((uint32_t)(c + 1u - lo0 < n0) << 1) |
                                                ((uint32_t)(c - lo1 < n1) << 2) | ((uint32_t)(c + 1u - lo1 < n1) << 3);
-                        if (qmask != 0u && !MI_ABLATE(1 << 17)) {
+                        if (qmask != 0u) {
                             const uint32_t gg = q0 >> 22;
                             const uint32_t slot = atomicAdd(&s_cnt[(ty - by0) * gx + tx], 1u);
-                            if (!MI_ABLATE(1 << 19)) entries[slot] = make_uint2(w_key[gg], w_id[gg] | (qmask << ID_BITS));
+                            entries[slot] = make_uint2(w_key[gg], w_id[gg] | (qmask << ID_BITS));
                         }
                     }
                 }

@@ -46,7 +46,7 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
     int W, int H, const float* __restrict__ bg_color, const float* __restrict__ colors,
     const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels,
     const float* __restrict__ dL_dout_mask, float* __restrict__ gpack /*[P,8] packed field gradients*/,
-    float* __restrict__ dL_dcolors, int ablate /* timing experiments only (MI_RAST_ABLATE); 0 in production */)
+    float* __restrict__ dL_dcolors)
 {
     constexpr bool WIDE = (C >= 32);           // transposed LDS reduction for the colour channels
     constexpr bool GEO = (C > 0);              // geometric gradients exist (not the mask-only pair)
@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
     auto flush = [&]() {
         // LDS rows written by this wave's own lanes: wave-local, no workgroup barrier needed
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        const int n = MI_ABLATE(2) ? 0 : __builtin_amdgcn_readfirstlane(nslots);
+        const int n = __builtin_amdgcn_readfirstlane(nslots);
         if constexpr (WIDE) {
             float sum[SLOTS];
 #pragma unroll
@@ -199,7 +199,6 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
     };
     // quad-reduce a per-pixel value and park the 16 partials of field `fi` of the current slot
     auto park = [&](int fi, float v) {
-        if MI_ABLATE(4) return;
         v += dpp_mov<0xB1>(v);
         v += dpp_mov<0x4E>(v);
         const int n = __builtin_amdgcn_readfirstlane(nslots);
@@ -228,7 +227,6 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
         // ---- B: features of this batch; clear the tile accumulators
         if constexpr (WIDE) {
             constexpr int F4 = C / 4;
-            if (!MI_ABLATE(32))
 #pragma unroll
             for (int k = 0; k < ROWS * F4 / BATCH; k++) {
                 const int q = tid + BATCH * k;
@@ -257,7 +255,6 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
                 npm = s_pm[rn];
                 const int pos = (int)(pm >> 4);  // 0-based forward position in the tile list
                 if (!((pm >> wave) & 1u) || pos >= wave_Lt) continue;
-                if MI_ABLATE(64) continue;
                 const float dx = cxy.x - pixfx, dy = cxy.y - pixfy;
                 const float power = gauss_power(-0.5f * cco.x, -cco.y, -0.5f * cco.z, dx, dy);
                 const float G = gauss_exp<XEXP>(power);
@@ -266,7 +263,6 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
                 // the forward's test, on t (min(0.99, t) >= 1/255 <=> t >= 1/255; false for a NaN t like there)
                 const bool valid = (pos < last_contributor) && power <= 0.0f && t >= (1.0f / 255.0f);
                 if (ballot64(valid) == 0) continue;
-                if MI_ABLATE(16) continue;
 
                 const float one_m_alpha_inv = __builtin_amdgcn_rcpf(1.f - alpha);
                 T = valid ? T * one_m_alpha_inv : T;
@@ -276,7 +272,6 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
                     park(6, w * dL_dout_mask_i);
                 } else {
                     float S0 = 0.f, S1 = 0.f;
-                    if (!MI_ABLATE(8))
 #pragma unroll
                     for (int ch = 0; ch < C; ch += 2) {
                         S0 = fmaf(s_feat[r * ROW + ch], dL_dpixel[ch], S0);
@@ -319,7 +314,6 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
             flush();
         }
         __syncthreads();
-        if MI_ABLATE(1) continue;
 
         // ---- D: one HBM atomic per touched (tile, Gaussian): C channels (128 B at C=32) + one packed 32-B record
         if constexpr (C > 0 && !WIDE) {

@@ -1,5 +1,5 @@
 // blend_bwd_shared.h -- constants and the staged-record type shared by the MFMA backward blend kernels
-// (blend_bwd_wave.h: the product kernel; blend_bwd_mfma.h: round 1's tile-batched kernel, profiling build only).
+// (blend_bwd_wave.h: the product kernel; blend_bwd_feat.h: the features-only backward).
 #pragma once
 
 #include "common.h"

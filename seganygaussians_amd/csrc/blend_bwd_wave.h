@@ -1,13 +1,13 @@
 // blend_bwd_wave.h -- per-QUADRANT back-to-front gradient pass: one wave per 8x8 pixel quadrant, no workgroup barriers.
 //
-// Same mathematics and the same 16-row MFMA chunk as blend_bwd_mfma.h (renderCUDA<C> backward,
+// Same mathematics and the same 16-row MFMA chunk as round 1's tile-batched MFMA kernel, since removed (renderCUDA<C> backward,
 // CF/cuda_rasterizer/backward.cu:399-559, with the three contractions S = F dL^T, dF = W^T dL, M = U^T Phi on
 // v_mfma_f32_16x16x4_f32); what changes is who walks the tile's blend list and when.
 //
-// blend_bwd_mfma.h stages the list in batches of 64 records for the whole tile; each of the four waves then picks its
-// quadrant's records out of the batch and pads them to a multiple of 16 rows PER BATCH: on cfg3 18 % of all chunk rows
-// are padding, the waves of a tile meet at two barriers per batch (14 % of wave time), and a wave with few rows idles
-// while the tile's busiest quadrant works.  Here a workgroup IS one wave:
+// That kernel staged the list in batches of 64 records for the whole tile; each of the four waves then picked its
+// quadrant's records out of the batch and padded them to a multiple of 16 rows PER BATCH: on cfg3 18 % of all chunk rows
+// were padding, the waves of a tile met at two barriers per batch (14 % of wave time), and a wave with few rows idled
+// while the tile's busiest quadrant worked.  Here a workgroup IS one wave:
 //   * the wave scans the tile's blend list itself, 64 entries at a time (four bytes each: Gaussian id | quadrant mask << 28,
 //     binning.h; prefetched one block ahead), and appends the entries of its quadrant to a ring in LDS (128 entries = 8 chunks
 //     of run-ahead), so chunks are always full -- only the wave's very last chunk is padded;

@@ -50,8 +50,7 @@ __global__ void __launch_bounds__(256, (C == 32 && EXTRA == 0) ? 4 : 1) blend_fw
     float* __restrict__ out_mask, float* __restrict__ out_depth,
     int cstride /* floats between the feature rows of two Gaussians: C, or the full channel count when this launch renders one
                    channel block of a wider feature (mi_rast.hip: channel blocks; `features` then points at the block) */,
-    int cr_arg /* PARTIAL: channels of this block that exist (1 .. C - 1) */,
-    int ablate /* timing experiments only (MI_RAST_ABLATE_FWD); 0 in production */)
+    int cr_arg /* PARTIAL: channels of this block that exist (1 .. C - 1) */)
 {
     const int cr = PARTIAL ? cr_arg : C;
     constexpr int CE = C + EXTRA;            // accumulated values per pixel
@@ -152,24 +151,22 @@ __global__ void __launch_bounds__(256, (C == 32 && EXTRA == 0) ? 4 : 1) blend_fw
             constexpr int F4 = C / 4;  // float4s per Gaussian
             // All the loads are issued before the first LDS write (unconditionally: a clamped row index keeps the
             // address valid) -- written as one guarded load-then-store per k, hipcc emits a full vmcnt(0) round trip per k.
-            if (!MI_ABLATE(4)) {
-                constexpr int NK = FB * F4 / BATCH;
-                float4 v[NK];
+            constexpr int NK = FB * F4 / BATCH;
+            float4 v[NK];
 #pragma unroll
-                for (int k = 0; k < NK; k++) {
-                    const int q = tid + BATCH * k;
-                    const int g = q / F4, part = q % F4;
-                    v[k] = reinterpret_cast<const float4*>(features + (size_t)s_id[g < nb ? g : 0] * cstride)[part];
-                }
-                // pins every loaded value in registers here: hipcc otherwise sinks each load into the guarded store below
-                #pragma unroll
-                for (int k = 0; k < NK; k++) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y), "+v"(v[k].z), "+v"(v[k].w));
+            for (int k = 0; k < NK; k++) {
+                const int q = tid + BATCH * k;
+                const int g = q / F4, part = q % F4;
+                v[k] = reinterpret_cast<const float4*>(features + (size_t)s_id[g < nb ? g : 0] * cstride)[part];
+            }
+            // pins every loaded value in registers here: hipcc otherwise sinks each load into the guarded store below
+            #pragma unroll
+            for (int k = 0; k < NK; k++) asm volatile("" : "+v"(v[k].x), "+v"(v[k].y), "+v"(v[k].z), "+v"(v[k].w));
 #pragma unroll
-                for (int k = 0; k < NK; k++) {
-                    const int q = tid + BATCH * k;
-                    const int g = q / F4, part = q % F4;
-                    if (g < nb) s_feat4[g * F4 + part] = v[k];
-                }
+            for (int k = 0; k < NK; k++) {
+                const int q = tid + BATCH * k;
+                const int g = q / F4, part = q % F4;
+                if (g < nb) s_feat4[g * F4 + part] = v[k];
             }
         }
         __syncthreads();

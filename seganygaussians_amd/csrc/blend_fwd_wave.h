@@ -24,50 +24,19 @@
 
 namespace mirast {
 
-// workgroup -> (tile, quadrant): every XCD works through contiguous runs of tiles, the four quadrants of a tile on four of its
-// waves at about the same time (common.h; id = 8 (4 j + quad) + x: XCD x, j-th tile of its runs).  The row-major tile sequence is
-// cut into 8 m runs of equal tile counts, run i to XCD i % 8: m = 1 is the one contiguous eighth of the image per XCD of rounds
-// 3-4; with m > 1 every XCD works on m bands spread over the image -- what a tile costs varies over the image of a real scene, and
-// nothing balances the XCDs' TIME but the statistics of what each is handed (a fast XCD cannot take more: the dispatcher deals
-// workgroup b to XCD b % 8 whatever their progress; profiles/r04_xcd_balance.md) -- at the price of more run boundaries, where
-// neighbouring tiles fetch the Gaussians they share into two L2s.
-__host__ __device__ inline uint32_t fwd_runs_longest(uint32_t ntiles, uint32_t m)   // tiles of the XCD that is handed the most
-{
-    uint32_t longest = 0;
-    for (uint32_t x = 0; x < 8u; x++) {
-        uint32_t t = 0;
-        for (uint32_t k = 0; k < m; k++) {
-            const uint32_t i = x + 8u * k;
-            t += (uint32_t)(((uint64_t)(i + 1u) * ntiles) / (8u * m)) - (uint32_t)(((uint64_t)i * ntiles) / (8u * m));
-        }
-        longest = t > longest ? t : longest;
-    }
-    return longest;
-}
-// m == 0: ONE run per XCD with the boundaries the range scan left in the image buffer (binning.h: tile_ranges_kernel, equal MODELLED
-// work); the grid is sized for the longest run.
-__device__ __forceinline__ bool fwd_wave_item(uint32_t b, uint32_t ntiles, uint32_t m, const uint32_t* __restrict__ run_bounds,
-                                              uint32_t& tile, uint32_t& quad)
+// workgroup -> (tile, quadrant): every XCD works through ONE contiguous run of tiles, the four quadrants of a tile on four of its
+// waves at about the same time (common.h; id = 8 (4 j + quad) + x: XCD x, j-th tile of its run).  The boundaries are the ones the
+// range scan left in the image buffer (binning.h: tile_ranges_kernel, runs of equal MODELLED work: what a tile costs varies over the
+// image of a real scene, and a fast XCD cannot take more -- the dispatcher deals workgroup b to XCD b % 8 whatever their progress;
+// profiles/r04_xcd_balance.md, r05_xcd_balance.md); the grid is sized for the longest run, ids beyond a run's length have no item.
+__device__ __forceinline__ bool fwd_wave_item(uint32_t b, const uint32_t* __restrict__ run_bounds, uint32_t& tile, uint32_t& quad)
 {
     const uint32_t x = b & 7u, jj = b >> 3;
-    uint32_t tl = jj >> 2;   // index into the concatenation of XCD x's m runs
+    const uint32_t tl = jj >> 2;   // index into XCD x's run
     quad = jj & 3u;
-    if (m == 0u) {
-        const uint32_t start = run_bounds[x], len = run_bounds[x + 1u] - start;
-        tile = start + tl;
-        return tl < len;
-    }
-    for (uint32_t k = 0; k < m; k++) {
-        const uint32_t i = x + 8u * k;
-        const uint32_t start = (uint32_t)(((uint64_t)i * ntiles) / (8u * m));
-        const uint32_t len = (uint32_t)(((uint64_t)(i + 1u) * ntiles) / (8u * m)) - start;
-        if (tl < len) {
-            tile = start + tl;
-            return true;
-        }
-        tl -= len;
-    }
-    return false;
+    const uint32_t start = run_bounds[x], len = run_bounds[x + 1u] - start;
+    tile = start + tl;
+    return tl < len;
 }
 
 // Zero-fill riding on the forward blend (include/mi_rast.h: dL_dcolor_next, MI_RAST_PREZERO_BWD).  The backward accumulates
@@ -101,11 +70,11 @@ constexpr int FWD_WAVES32 = 4, FWD_WAVES64 = 3;
 template <int C, int XM = EXP_HYBRID, bool STRIDED = false, bool PARTIAL = false>
 __global__ void __launch_bounds__(64, C == 32 ? FWD_WAVES32 : FWD_WAVES64) blend_fwd_wave_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ blend_list, const BlendRec* __restrict__ index_rec,
-    int W, int H, uint32_t horizontal_blocks, uint32_t ntiles, const float* __restrict__ features, float* __restrict__ final_T,
+    int W, int H, uint32_t horizontal_blocks, const float* __restrict__ features, float* __restrict__ final_T,
     uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ tile_consumed /* zeroed: receives atomicMax */,
     uint32_t* __restrict__ tile_nsurv /* zeroed: receives atomicMax */, const float* __restrict__ bg_color,
     float* __restrict__ out_color, int cstride_arg /* STRIDED: floats between feature rows (blend_fwd.h) */, FwdZeroFill zfill,
-    uint32_t runs_per_xcd /* fwd_wave_item's m */, const uint32_t* __restrict__ run_bounds /* [9], m == 0 */,
+    const uint32_t* __restrict__ run_bounds /* [9]: the XCD runs of tiles (fwd_wave_item) */,
     int cr_arg /* PARTIAL: channels of this block that exist (1 .. 31) */)
 {
     static_assert(C == 32 || C == 64, "32-channel accumulator blocks");
@@ -125,7 +94,7 @@ __global__ void __launch_bounds__(64, C == 32 ? FWD_WAVES32 : FWD_WAVES64) blend
 
     fwd_zero_fill(zfill, blockIdx.x, gridDim.x, (int)(threadIdx.x & 63));   // (every workgroup, also those without an item)
     uint32_t tile, quad;
-    if (!fwd_wave_item(blockIdx.x, ntiles, runs_per_xcd, run_bounds, tile, quad)) return;
+    if (!fwd_wave_item(blockIdx.x, run_bounds, tile, quad)) return;
     MI_XCD_STAMP(false);   // (profiling build: per-XCD start / end stamps, common.h)
     const int lane = threadIdx.x & 63;
     const uint32_t tile_x = tile % horizontal_blocks, tile_y = tile / horizontal_blocks;
@@ -455,11 +424,11 @@ namespace mirast {
 template <int EXTRA, int XM = EXP_HYBRID>
 __global__ void __launch_bounds__(64, 8) blend_fwd_wave_rgb_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ blend_list, const BlendRec* __restrict__ index_rec,
-    int W, int H, uint32_t horizontal_blocks, uint32_t ntiles, const float* __restrict__ features /* [P,3] */,
+    int W, int H, uint32_t horizontal_blocks, const float* __restrict__ features /* [P,3] */,
     const float* __restrict__ mask, const float* __restrict__ depths, float* __restrict__ final_T,
     uint32_t* __restrict__ n_contrib, uint32_t* __restrict__ tile_consumed, uint32_t* __restrict__ tile_nsurv,
     const float* __restrict__ bg_color, float* __restrict__ out_color, float* __restrict__ out_mask, float* __restrict__ out_depth,
-    FwdZeroFill zfill, uint32_t runs_per_xcd, const uint32_t* __restrict__ run_bounds)
+    FwdZeroFill zfill, const uint32_t* __restrict__ run_bounds)
 {
     constexpr int C = 3, CE = C + EXTRA, QCAP = 128, FROW = 8;
     __shared__ XRec s_rec[XG];
@@ -470,7 +439,7 @@ __global__ void __launch_bounds__(64, 8) blend_fwd_wave_rgb_kernel(
 
     fwd_zero_fill(zfill, blockIdx.x, gridDim.x, (int)(threadIdx.x & 63));   // (every workgroup, also those without an item)
     uint32_t tile, quad;
-    if (!fwd_wave_item(blockIdx.x, ntiles, runs_per_xcd, run_bounds, tile, quad)) return;
+    if (!fwd_wave_item(blockIdx.x, run_bounds, tile, quad)) return;
     const int lane = threadIdx.x & 63;
     const uint32_t tile_x = tile % horizontal_blocks, tile_y = tile / horizontal_blocks;
     const uint32_t px = tile_x * TILE_X + (quad & 1) * 8 + (lane & 7);

@@ -11,15 +11,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Timing experiments (pieces of a kernel switched off by a run-time bit mask; results become wrong) exist only in the
-// profiling build (-DMI_RAST_PROFILING -> libmi_rast_prof.so).  In the product build MI_ABLATE(bit) is the constant
-// `false`, so the kernels carry no dead branches and the `ablate` argument is unused.
-#ifdef MI_RAST_PROFILING
-#define MI_ABLATE(bit) (((ablate) & (bit)) != 0)
-#else
-#define MI_ABLATE(bit) (false)
-#endif
-
 // Per-wave time stamps of the blend kernels, PROFILING build only (tools/xcd_stamps.py; mi_rast_xcd_stamps in mi_rast.hip): a wave's
 // first lane stores the constant 100-MHz clock at its start (with the XCD it runs on) and at its end into ITS OWN two words -- plain
 // stores: stamps kept with atomics on sixteen shared words slowed the kernels by half.  The product build compiles the macro to nothing.
@@ -230,11 +221,10 @@ constexpr uint32_t XCD_QUEUE_DIV = 2;  // the queued part of a run is its last 1
 // to XCD b % 8 whatever the XCDs' progress.  The range scan (binning.h: tile_ranges_kernel) therefore cuts the row-major tile
 // sequence into eight contiguous runs of equal MODELLED work, sum(min(list length, 768) + 128) -- the list LENGTH alone is the wrong
 // weight: an opaque surface ends a long list early --, and leaves the nine boundaries in the image buffer for both blend kernels
-// (profiles/r05_xcd_balance.md: cfg3s +7 %).  A knob (mi_rast.hip: BWD_RUNS_FROM_WALKS, off) replaces the backward's boundaries by
-// ones cut at equal sums of what the forward really WALKED (tile_nsurv + XCD_TILE_WEIGHT; run_bounds_from_walks_kernel, one more
-// launch behind the forward blend).  A run holds at most XCD_MAX_RUN_FACTOR times the equal share: that bounds the grid the
-// (stateless) backward launches -- ids beyond a run's length exit at once.
-constexpr uint32_t XCD_TILE_WEIGHT = 128;     // a tile's fixed cost (four waves' start-up) in list entries: 32 / 128 / 256 measured, round 4
+// (profiles/r05_xcd_balance.md: cfg3s +7 %).  (Cutting the backward's runs at equal sums of what the forward really WALKED instead,
+// one more launch behind the forward blend, gained nothing in round 6 and was removed: DESIGN.md section 11.)  A run holds at most
+// XCD_MAX_RUN_FACTOR times the equal share: that bounds the grid the (stateless) backward launches -- ids beyond a run's length exit
+// at once.
 constexpr uint32_t XCD_MAX_RUN_FACTOR = 2;
 struct XcdRuns {
     uint32_t b[9];   // run x = tiles [b[x], b[x + 1])

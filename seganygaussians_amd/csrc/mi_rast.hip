@@ -209,7 +209,7 @@ struct ImgPtrs {
     int* num_rendered;
     uint32_t* tile_nsurv;   // per tile: blend-list entries the forward walked
     uint32_t* run_bounds;   // [9]: the blend kernels' XCD runs of tiles (common.h: XcdRuns): from the range scan (equal counts, or equal
-                            // modelled work), replaced by run_bounds_from_walks_kernel behind the forward blend when that is switched on
+                            // modelled work)
     uint32_t longest_run;   // host copy of the longest of those runs (forward only: read from the pinned words at the ev2 wait)
 };
 struct BinPtrs {
@@ -266,19 +266,6 @@ BinPtrs bin_from(char* base, int R)
     return b;
 }
 
-// Timing experiments exist only in the profiling build (-DMI_RAST_PROFILING, seganygaussians_amd/build.py:
-// libmi_rast_prof.so): MI_RAST_ABLATE / MI_RAST_ABLATE_FWD=<bitmask> disable pieces of the blend kernels (results become
-// wrong).  The product build compiles none of it: no getenv, no run-time switches inside the kernels (common.h: MI_ABLATE).
-#ifdef MI_RAST_PROFILING
-int ablate_env(const char* name)
-{
-    const char* ab = getenv(name);
-    return ab ? atoi(ab) : 0;
-}
-#else
-constexpr int ablate_env(const char*) { return 0; }
-#endif
-
 // One-time opt-in to > 64 KB of dynamic LDS (gfx950: 160 KB per workgroup), per device.
 std::atomic<bool> g_attr_set[MAX_DEVICES];
 std::mutex g_attr_mutex;
@@ -302,32 +289,15 @@ bool channels_supported(int c) { return c >= 1 && c <= MAX_CHANNELS; }
 // next block of a feature with `rem` channels left (rem < 16: a 16-channel block of which `rem` exist)
 int channel_block(int rem) { return rem >= 64 ? 64 : (rem >= 32 ? 32 : 16); }
 
-// How the blend kernels' tiles are dealt to the eight XCDs (common.h, blend_fwd_wave.h: fwd_wave_item, binning.h: tile_ranges_kernel).
-// Product constants; the profiling build reads overrides from the environment for A/B runs (MI_RAST_FWD_RUNS, MI_RAST_RUN_CAP,
-// MI_RAST_RUN_FIX, MI_RAST_BWD_SCAN).
+// How the blend kernels' tiles are dealt to the eight XCDs (common.h, blend_fwd_wave.h: fwd_wave_item, binning.h: tile_ranges_kernel):
+// one run of tiles per XCD, both blend kernels, boundaries from the range scan.
 // Measured in round 5 (profiles/r05_xcd_balance.md; cfg3s = density varying over the image, cfg3 = uniform): equal tile counts 447 / 844
 // views/s; this model 493 / 835 (cap 384 ... 1024, fix 32 ... 128 tried: 768 / 128 best; no cap -- the list length -- 428: a long list
 // on an opaque surface is a SHORT walk); m = 4 interleaved equal-count runs in the forward + the walk scan for the backward 497 / 831.
-constexpr int FWD_RUNS_PER_XCD = 0;   // forward: m interleaved runs of equal tile counts per XCD; 0: one run per XCD, boundaries from the range scan
+// (Both of those were removed later; so was cutting the backward's runs at what the forward really walked, measured in round 6 at
+// 530.2 / 529.1 / 530.8 views/s for never / when the density varies / always -- DESIGN.md section 11.)
 constexpr int RUN_MODEL_CAP = 768;    // range scan: XCD runs of equal sum(min(list length, cap) + fix); 0: equal tile counts
-constexpr int RUN_MODEL_FIX = 128;
-// Forward of a view to be differentiated: the backward's runs from what the forward really WALKED (run_bounds_from_walks_kernel, one more
-// 9-us launch behind the forward blend).  0 (product): never; 1: always; 2: when the range scan's model says the scene's density varies
-// over the image (its longest run exceeds the equal share by more than an eighth).  Round 6 (tools/xcd_stamps.py: per-XCD finish times
-// from per-wave stamps): with the model runs the backward's XCDs finish within 6-7 % of each other on the uniform law (cfg3) and within
-// 21 % on the second law (cfg3s; the model balances the FORWARD: 11-13 %); the exact walks take 1.6 % off that backward (1.099 -> 1.081 ms)
-// and put their launch on the forward: 530.2 / 529.1 / 530.8 views/s for 0 / 2 / 1 -- nothing, so it stays a knob.
-constexpr int BWD_RUNS_FROM_WALKS = 0;
-inline int knob(const char* name, int dflt)
-{
-#ifdef MI_RAST_PROFILING
-    const char* e = getenv(name);
-    if (e) return atoi(e);
-#endif
-    (void)name;
-    return dflt;
-}
-inline uint32_t fwd_runs_per_xcd() { return (uint32_t)std::min(16, std::max(0, knob("MI_RAST_FWD_RUNS", FWD_RUNS_PER_XCD))); }
+constexpr int RUN_MODEL_FIX = 128;    // a tile's fixed cost (four waves' start-up) in list entries
 inline uint32_t longest_of(const int* bounds, uint32_t ntiles)
 {
     uint32_t longest = 0;
@@ -349,8 +319,6 @@ int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user,
     const int dev = current_device();
     if (dev < 0) return fail(MI_RAST_ERR_HIP, "hipGetDevice failed (or device ordinal >= 64)");
     HostSync& g_host_sync = g_host_sync_tl[dev];
-    const int g_ablate_fwd = ablate_env("MI_RAST_ABLATE_FWD");
-    (void)g_ablate_fwd;
     size_t goff[MI_GEOM_NFIELDS], ioff[MI_IMG_NFIELDS];
     const size_t geom_size = mi_rast_geometry_layout(P, goff);
     char* geom_base = geometry_buffer(geom_size, geometry_user);
@@ -409,8 +377,6 @@ int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user,
             HIP_TRY(hipFuncSetAttribute((const void*)bin_spans_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
             HIP_TRY(hipFuncSetAttribute((const void*)tile_ranges_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                         (BIN_MAX_TILES_TOTAL + 1) * (int)sizeof(uint32_t)));
-            HIP_TRY(hipFuncSetAttribute((const void*)run_bounds_from_walks_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (BIN_MAX_TILES_TOTAL + 1) * (int)sizeof(uint32_t)));
             g_attr_set[dev].store(true, std::memory_order_release);
         }
     }
@@ -423,10 +389,7 @@ int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user,
     const bool full = debug != 0 || nocull || (flags & MI_RAST_FULL_LISTS) != 0;
     // full lists: <= 256 workgroups of 1024 threads, each a slice of the Gaussians (64-index chunks dealt round robin); lean lists:
     // workgroups dealt to the bands in proportion to the bands' Gaussian counts (binning.h: band_plan), at least one per band
-    int nwg = full ? bin_workgroups(P) : std::min(knob("MI_RAST_LEAN_NWG", BIN_LEAN_WG), (int)lean_nbands + (P + 1023) / 1024);
-#ifdef MI_RAST_PROFILING
-    if (ablate_env("MI_RAST_NWG") > 0) nwg = std::min(nwg, ablate_env("MI_RAST_NWG"));
-#endif
+    const int nwg = full ? bin_workgroups(P) : std::min(BIN_LEAN_WG, (int)lean_nbands + (P + 1023) / 1024);
     const size_t band_tiles = (size_t)band_rows * vp.grid_x;
     const size_t bin_lds = ((size_t)((band_tiles + 3) & ~(size_t)3) + 3 * 1024 + 16) * sizeof(uint32_t);
     {
@@ -443,7 +406,7 @@ int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user,
         if (!full)
             hipLaunchKernelGGL(bin_spans_kernel<false>, dim3(nwg), dim3(1024), span_lds_bytes((size_t)lean_band_h * count_grid_stride(vp.grid_x)),
                                stream, P, geom.index_rec, geom.depth_key, geom.band_bits, img.tile_count, img.tile_cursor, (const uint2*)nullptr, (uint2*)nullptr,
-                               vp.grid_x, vp.grid_y, lean_band_h, lean_nbands, (const int*)img.num_rendered, g_host_sync.pinned_dev, g_ablate_fwd);
+                               vp.grid_x, vp.grid_y, lean_band_h, lean_nbands, (const int*)img.num_rendered, g_host_sync.pinned_dev);
         HIP_TRY(hipEventRecord(g_host_sync.ev, stream));
         // (one launch for both scans -- every workgroup scans its tiles over the slices, the last one to finish scans the totals
         // behind a device-scope counter and agent-scope fences -- was built and measured in round 4: tile scan 0.058 -> 0.060 ms
@@ -452,8 +415,8 @@ int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user,
         if (full)
             hipLaunchKernelGGL(scan_partials_kernel, dim3((ntiles + 63) / 64), dim3(1024), 0, stream, ntiles, nwg,
                                img.tile_count, img.tile_cursor);
-        const uint32_t run_cap = !(flags & MI_RAST_EQUAL_RUNS) ? (uint32_t)std::max(0, knob("MI_RAST_RUN_CAP", RUN_MODEL_CAP)) : 0u;
-        const uint32_t run_fix = (uint32_t)std::max(0, knob("MI_RAST_RUN_FIX", RUN_MODEL_FIX));
+        const uint32_t run_cap = !(flags & MI_RAST_EQUAL_RUNS) ? (uint32_t)RUN_MODEL_CAP : 0u;
+        const uint32_t run_fix = (uint32_t)RUN_MODEL_FIX;
         hipLaunchKernelGGL(tile_ranges_kernel, dim3(1), dim3(1024),
                            ((size_t)std::min(ntiles, BIN_MAX_TILES_TOTAL) + 1) * sizeof(uint32_t), stream, ntiles, img.tile_cursor,
                            img.ranges, img.num_rendered + R_SLOTS * R_SLOT_STRIDE, (const int*)img.num_rendered,
@@ -478,10 +441,6 @@ int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user,
     const bool verify = !full && (flags & MI_RAST_VERIFY_LISTS) != 0;
     if (R > 0) {
         if (verify) HIP_TRY(hipMemsetAsync(bin.entries, 0, (size_t)R * sizeof(uint2), stream));
-#ifdef MI_RAST_PROFILING
-        // timing experiments that leave list slots unwritten (tools/abl_emit.sh): zeros instead of stale ids, so that the blends stay in bounds
-        if (g_ablate_fwd & ((1 << 16) | (1 << 17) | (1 << 19) | (1 << 20))) HIP_TRY(hipMemsetAsync(bin.entries, 0, (size_t)R * sizeof(uint2), stream));
-#endif
         {
             StageTimer t(stream, MI_STAGE_EMIT);
             const size_t emit_lds = bin_lds + 8 * 1024 * sizeof(uint32_t);
@@ -497,7 +456,7 @@ int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user,
             if (!full)
                 hipLaunchKernelGGL(bin_spans_kernel<true>, dim3(nwg), dim3(1024), span_lds_bytes((size_t)lean_band_h * vp.grid_x), stream, P,
                                    geom.index_rec, geom.depth_key, geom.band_bits, img.tile_count, img.tile_cursor, img.ranges, bin.entries, vp.grid_x, vp.grid_y,
-                                   lean_band_h, lean_nbands, (const int*)img.num_rendered, (int*)nullptr, g_ablate_fwd);
+                                   lean_band_h, lean_nbands, (const int*)img.num_rendered, (int*)nullptr);
         }
         STAGE_CHECK("emit entries");
         if (verify) {   // debugging aid: synchronous
@@ -557,11 +516,10 @@ void launch_blend_fwd(const ViewParams& vp, hipStream_t stream, const ImgPtrs& i
                       const GeomPtrs& geom, const float* features, const float* mask, const float* bg,
                       float* out_color, float* out_mask, float* out_depth, bool xexp, int cstride = C, int cr = C)
 {
-    const int g_ablate_fwd = ablate_env("MI_RAST_ABLATE_FWD");
 #define TILE_FWD_LAUNCH(XE, PART)                                                                                                     \
     hipLaunchKernelGGL((blend_fwd_kernel<C, EXTRA, XE, PART>), dim3(vp.grid_x, vp.grid_y), dim3(256), 0, stream, img.ranges,              \
                        bin.blend_list, geom.index_rec, vp.W, vp.H, features, mask, geom.depths, img.final_T, img.n_contrib,              \
-                       img.tile_consumed, img.tile_nsurv, bg, out_color, out_mask, out_depth, cstride, cr, g_ablate_fwd)
+                       img.tile_consumed, img.tile_nsurv, bg, out_color, out_mask, out_depth, cstride, cr)
     if constexpr (C == 16 && EXTRA == 0) {   // the remainder block of a feature: `cr` < 16 of its channels may exist (blend_fwd.h PARTIAL)
         if (cr < C) {
             if (xexp) TILE_FWD_LAUNCH(true, true);
@@ -601,14 +559,13 @@ void launch_blend_fwd_wave(const ViewParams& vp, hipStream_t stream, const ImgPt
                            const float* features, const float* bg, float* out_color, int xm, int cstride, FwdZeroFill& zfill, int cr = C)
 {
     const uint32_t nt = vp.grid_x * vp.grid_y;
-    const uint32_t fm = fwd_runs_per_xcd();
-    const uint32_t grid = 32u * (fm ? fwd_runs_longest(nt, fm) : (img.longest_run ? img.longest_run : xcd_max_run(nt)));
+    const uint32_t grid = 32u * (img.longest_run ? img.longest_run : xcd_max_run(nt));
     const FwdZeroFill zf = zfill;
     zfill = FwdZeroFill{nullptr, 0u, nullptr, 0u};   // taken: the launches of further channel blocks fill nothing
 #define FW_LAUNCH(XM, ST, PT)                                                                                                 \
     hipLaunchKernelGGL((blend_fwd_wave_kernel<C, XM, ST, PT>), dim3(grid), dim3(64), 0, stream, img.ranges, bin.blend_list,       \
-                       geom.index_rec, vp.W, vp.H, vp.grid_x, nt, features, img.final_T, img.n_contrib, img.tile_consumed,        \
-                       img.tile_nsurv, bg, out_color, cstride, zf, fm, img.run_bounds, cr)
+                       geom.index_rec, vp.W, vp.H, vp.grid_x, features, img.final_T, img.n_contrib, img.tile_consumed,        \
+                       img.tile_nsurv, bg, out_color, cstride, zf, img.run_bounds, cr)
 #define FW_LAUNCH_ST(ST, PT)                                  \
     do {                                                      \
         if (xm == EXP_HYBRID) FW_LAUNCH(EXP_HYBRID, ST, PT);  \
@@ -633,14 +590,13 @@ void launch_blend_fwd_wave_rgb(const ViewParams& vp, hipStream_t stream, const I
                                float* out_depth, int xm, FwdZeroFill& zfill)
 {
     const uint32_t nt = vp.grid_x * vp.grid_y;
-    const uint32_t fm = fwd_runs_per_xcd();
-    const uint32_t grid = 32u * (fm ? fwd_runs_longest(nt, fm) : (img.longest_run ? img.longest_run : xcd_max_run(nt)));
+    const uint32_t grid = 32u * (img.longest_run ? img.longest_run : xcd_max_run(nt));
     const FwdZeroFill zf = zfill;
     zfill = FwdZeroFill{nullptr, 0u, nullptr, 0u};
 #define RGB_LAUNCH(XM)                                                                                                                       \
     hipLaunchKernelGGL((blend_fwd_wave_rgb_kernel<EXTRA, XM>), dim3(grid), dim3(64), 0, stream, img.ranges, bin.blend_list, geom.index_rec,   \
-                       vp.W, vp.H, vp.grid_x, nt, features, mask, geom.depths, img.final_T, img.n_contrib, img.tile_consumed,                 \
-                       img.tile_nsurv, bg, out_color, out_mask, out_depth, zf, fm, img.run_bounds)
+                       vp.W, vp.H, vp.grid_x, features, mask, geom.depths, img.final_T, img.n_contrib, img.tile_consumed,                 \
+                       img.tile_nsurv, bg, out_color, out_mask, out_depth, zf, img.run_bounds)
     if (xm == EXP_HYBRID) RGB_LAUNCH(EXP_HYBRID);
     else if (xm == EXP_EXACT) RGB_LAUNCH(EXP_EXACT);
     else RGB_LAUNCH(EXP_FAST);
@@ -652,15 +608,14 @@ void launch_blend_bwd(const ViewParams& vp, hipStream_t stream, const ImgPtrs& i
                       const GeomPtrs& geom, const float* colors, const float* bg, const float* dL_dpix,
                       const float* dL_dout_mask, float* dL_dcolor, bool xexp)
 {
-    const int g_ablate = ablate_env("MI_RAST_ABLATE");
     if (xexp)
         hipLaunchKernelGGL((blend_bwd_kernel<C, MASKGRAD, true>), dim3(vp.grid_x, vp.grid_y), dim3(256), 0, stream, img.ranges,
                            bin.blend_list, geom.index_rec, img.tile_nsurv, vp.W, vp.H, bg, colors, img.final_T, img.n_contrib, dL_dpix,
-                           dL_dout_mask, geom.bwd_pack, dL_dcolor, g_ablate);
+                           dL_dout_mask, geom.bwd_pack, dL_dcolor);
     else
         hipLaunchKernelGGL((blend_bwd_kernel<C, MASKGRAD, false>), dim3(vp.grid_x, vp.grid_y), dim3(256), 0, stream, img.ranges,
                            bin.blend_list, geom.index_rec, img.tile_nsurv, vp.W, vp.H, bg, colors, img.final_T, img.n_contrib, dL_dpix,
-                           dL_dout_mask, geom.bwd_pack, dL_dcolor, g_ablate);
+                           dL_dout_mask, geom.bwd_pack, dL_dcolor);
 }
 
 }  // namespace
@@ -1087,7 +1042,7 @@ size_t mi_rast_image_layout(int width, int height, size_t* off)
     off[MI_IMG_RANGES] = c.take((tiles ? tiles : 1) * sizeof(uint2));
     off[MI_IMG_TILE_CONSUMED] = c.take((tiles ? tiles : 1) * sizeof(uint32_t));
     // tile_count holds partial[slice][tile] of the count / emit passes (binning.h); tile_cursor the tile totals
-    constexpr int max_slices = BIN_MAX_WG;   // (the lean passes' [workgroup][tile of its band] table is far smaller: BIN_LEAN_WG_MAX x a band's tiles)
+    constexpr int max_slices = BIN_MAX_WG;   // (the lean passes' [workgroup][tile of its band] table is far smaller: BIN_LEAN_WG x a band's tiles)
     off[MI_IMG_TILE_COUNT] = c.take((size_t)max_slices * (tiles ? tiles : 1) * sizeof(uint32_t));
     off[MI_IMG_TILE_CURSOR] = c.take((tiles ? tiles : 1) * sizeof(uint32_t));
     off[MI_IMG_NUM_RENDERED] = c.take((R_SLOTS * R_SLOT_STRIDE + 16) * sizeof(int));  // R partial sums, then {R, longest list}, then the nine run boundaries
@@ -1200,8 +1155,8 @@ static int blend_forward_stage(const ViewParams& vp, hipStream_t stream, GeomPtr
         }
         const bool xexp = (flags & MI_RAST_FAST_EXP) == 0;   // the kernels without a hybrid form: expf unless MI_RAST_FAST_EXP
         const int xm = (flags & MI_RAST_FAST_EXP) ? EXP_FAST : (flags & MI_RAST_EXACT_EXP) ? EXP_EXACT : EXP_HYBRID;   // the wave-per-quadrant kernels
-        // Product kernels: the wave-per-quadrant forward (RGB, RGB + mask + depth, 64- and 32-channel blocks) and the tile-batched kernel for
-        // the 16-channel remainder block.  The comparison kernels of earlier rounds -- MI_RAST_TILE_FWD (tile-batched bf16x3 / RGB),
+        // Product kernels: the wave-per-quadrant forward (RGB, RGB + mask + depth, 64- and 32-channel blocks; the remainder of a feature is a
+        // partial 32-channel block of the same kernel).  The comparison kernels of earlier rounds -- MI_RAST_TILE_FWD (tile-batched bf16x3 / RGB),
         // MI_RAST_F32_BLEND (f32 FMA chain) -- exist in the profiling build only (libmi_rast_prof.so, seganygaussians_amd/build.py).
 #ifdef MI_RAST_PROFILING
         const bool tile_fwd = (flags & MI_RAST_TILE_FWD) != 0, f32_blend = (flags & MI_RAST_F32_BLEND) != 0;
@@ -1262,15 +1217,6 @@ static int blend_forward_stage(const ViewParams& vp, hipStream_t stream, GeomPtr
         // no wave-per-quadrant launch took the fill (tile-batched / f32 / 16-channel kernels): fill commands
         if (zfill.na) HIP_TRY(hipMemsetAsync(zfill.a, 0, (size_t)zfill.na << 4, stream));
         if (zfill.nb) HIP_TRY(hipMemsetAsync(zfill.b, 0, (size_t)zfill.nb << 4, stream));
-        // A view that will be differentiated (the caller asked for the backward's buffers to be left zeroed): the backward blend's
-        // XCD runs from what this forward walked (common.h "WORK-balanced runs"; inside the forward blend's stage time)
-        const int nt_all = (int)(vp.grid_x * vp.grid_y);
-        const int walk_scan = knob("MI_RAST_BWD_SCAN", BWD_RUNS_FROM_WALKS);
-        const uint32_t equal_share = ((uint32_t)nt_all + 7u) >> 3;
-        if (((flags & MI_RAST_PREZERO_BWD) || dL_dcolor_next != nullptr) && nt_all <= BIN_MAX_TILES_TOTAL && !(flags & MI_RAST_EQUAL_RUNS) &&
-            (walk_scan == 1 || (walk_scan == 2 && img.longest_run > equal_share + (equal_share >> 3))))
-            hipLaunchKernelGGL(run_bounds_from_walks_kernel, dim3(1), dim3(1024), ((size_t)nt_all + 1) * sizeof(uint32_t), stream, nt_all,
-                               img.tile_nsurv, img.run_bounds);
     }
     STAGE_CHECK("render");
     return MI_RAST_OK;
@@ -1400,8 +1346,6 @@ int mi_rast_backward(int P, int D, int M, int channels, int R, const float* back
     hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0) return MI_RAST_OK;
     const bool xexp = (flags & MI_RAST_FAST_EXP) == 0;
-    const int g_ablate = ablate_env("MI_RAST_ABLATE");
-    (void)g_ablate;
     if (!channels_supported(channels)) return fail(MI_RAST_ERR_INVALID, "unsupported channel count (supported: 1 .. 256)");
     const bool maskgrad = dL_dmask != nullptr;
     if (maskgrad && (channels != 3 || !dL_dout_mask)) return fail(MI_RAST_ERR_INVALID, "mask gradient needs 3 channels and dL_dout_mask");
@@ -1446,14 +1390,6 @@ int mi_rast_backward(int P, int D, int M, int channels, int R, const float* back
         if (cstride == CR_) LAUNCH_BWD_WAVE_ST(false, C_, CR_, MG_);                \
         else LAUNCH_BWD_WAVE_ST(true, C_, CR_, MG_);                                \
     } while (0)
-#ifdef MI_RAST_PROFILING
-        if (g_ablate & 1024) {  // the VALU kernels (timing comparisons)
-            if (maskgrad) launch_blend_bwd<3, true>(vp, stream, img, bin, geom, color_ptr, background, dL_dpix, dL_dout_mask, dL_dcolor, xexp);
-            else if (channels == 3) launch_blend_bwd<3, false>(vp, stream, img, bin, geom, color_ptr, background, dL_dpix, nullptr, dL_dcolor, xexp);
-            else if (channels == 32) launch_blend_bwd<32, false>(vp, stream, img, bin, geom, color_ptr, background, dL_dpix, nullptr, dL_dcolor, xexp);
-            else launch_blend_bwd<64, false>(vp, stream, img, bin, geom, color_ptr, background, dL_dpix, nullptr, dL_dcolor, xexp);
-        } else
-#endif
         if (feat_only) {
             // one launch per channel block of 64 / 32 / 16 channels (blend_bwd_feat.h: one wave per half tile): alpha, T, dF = W^T dL and
             // the feature-row atomics

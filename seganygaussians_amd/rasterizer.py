@@ -664,8 +664,7 @@ def _make_plain(channels):
             # a backward will follow: its accumulators are zero-filled by the forward's blend kernel (rasterize_gaussians_native)
             # (needs_input_grad is requires_grad of the inputs whatever the grad mode: render.py's no_grad forwards of a model whose
             # parameters require grad would zero 128 MB per view for a backward that never comes)
-            prezero = (_opts.grad_mode and bool(any(ctx.needs_input_grad)) and not rs.debug
-                       and not os.environ.get("MI_RAST_NO_PREZERO"))   # (env: A/B aid)
+            prezero = _opts.grad_mode and bool(any(ctx.needs_input_grad)) and not rs.debug
 
             def call():
                 (bg, m3, col, op, sc, rot, smod, cov, vm, pm, tx, ty, ih, iw, sh_, deg, cp, pre, dbg) = args

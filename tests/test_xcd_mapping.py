@@ -1,16 +1,17 @@
 """CPU check of the blend kernels' workgroup -> (tile, quadrant) assignments (seganygaussians_amd/csrc/common.h: xcd_run_start,
-xcd_max_run, xcd_static_len_max, xcd_queued_tiles_max, xcd_clamp_runs, xcd_grab_runs; binning.h: run_bounds_from_walks_kernel;
-blend_bwd_wave.h: the end of the kernel; blend_fwd_wave.h: fwd_wave_item / fwd_runs_longest), restated in Python.
+xcd_max_run, xcd_static_len_max, xcd_queued_tiles_max, xcd_clamp_runs, xcd_grab_runs; binning.h: tile_ranges_kernel's runs;
+blend_bwd_wave.h: the end of the kernel; blend_fwd_wave.h: fwd_wave_item), restated in Python.
 
-Backward: the row-major tile sequence is cut into eight contiguous runs -- equal tile counts (what every forward's range scan
-leaves) or equal sums of (tile_nsurv + XCD_TILE_WEIGHT) (what the scan behind a forward that will be differentiated leaves),
-clamped to at most twice the equal share.  For ANY such boundaries the statically assigned ids and the queued items together
-cover every (tile, quadrant) exactly once, and the grid the stateless host launches (sized for the longest run the clamp allows)
-has an id for every static item and at least one taker per queued item.
-Forward: 8 m runs dealt to the XCDs round robin; every (tile, quadrant) has exactly one id in the grid."""
+Both blend kernels: the row-major tile sequence is cut into eight contiguous runs -- equal tile counts (MI_RAST_EQUAL_RUNS) or
+equal sums of a tile's modelled weight (the range scan's default), clamped to at most twice the equal share.
+Backward: for ANY such boundaries the statically assigned ids and the queued items together cover every (tile, quadrant) exactly
+once, and the grid the stateless host launches (sized for the longest run the clamp allows) has an id for every static item and
+at least one taker per queued item.
+Forward: one run per XCD; every (tile, quadrant) has exactly one id in the grid sized for the longest run."""
 import numpy as np
 
-QUEUE_DIV, MAX_RUN_FACTOR, TILE_WEIGHT = 2, 2, 128   # common.h
+QUEUE_DIV, MAX_RUN_FACTOR = 2, 2   # common.h
+TILE_WEIGHT = 128                  # a tile's fixed weight (mi_rast.hip: RUN_MODEL_FIX)
 
 
 def run_start(x, n):
@@ -42,7 +43,8 @@ def clamp_runs(b, n):
 
 
 def bounds_from_walks(nsurv):
-    """binning.h: run_bounds_from_walks_kernel."""
+    """The equal-weight cut of the XCD runs, per-tile weight nsurv + TILE_WEIGHT, and the clamp (common.h: xcd_clamp_runs) --
+    what tile_ranges_kernel does with its modelled weights (bounds_from_model)."""
     n = len(nsurv)
     w = np.concatenate([[0], np.cumsum(np.asarray(nsurv, np.int64) + TILE_WEIGHT)])
     total = int(w[-1])
@@ -94,6 +96,7 @@ def test_every_quadrant_exactly_once_for_any_runs():
 
 
 def test_runs_of_equal_walked_weight():
+    """The equal-weight cut and the clamp behind the range scan's model runs (bounds_from_model), on per-tile weights."""
     rng = np.random.default_rng(1)
     n = 120 * 68
     # a scene whose upper half is walked five times as deep as its lower half: the runs follow the weight, not the tile count
@@ -120,34 +123,8 @@ def test_runs_of_equal_walked_weight():
     assert wm.max() <= 1.05 * wm.mean(), wm
 
 
-def fwd_item(wg, n, m):
-    """blend_fwd_wave.h: fwd_wave_item."""
-    x, jj = wg & 7, wg >> 3
-    tl, quad = jj >> 2, jj & 3
-    for k in range(m):
-        i = x + 8 * k
-        start = (i * n) // (8 * m)
-        length = ((i + 1) * n) // (8 * m) - start
-        if tl < length:
-            return start + tl, quad
-        tl -= length
-    return None
-
-
-def fwd_longest(n, m):
-    return max(sum(((x + 8 * k + 1) * n) // (8 * m) - ((x + 8 * k) * n) // (8 * m) for k in range(m)) for x in range(8))
-
-
-def test_forward_runs_cover_every_quadrant_once():
-    for n in list(range(1, 40)) + [8160, 6700, 255]:
-        for m in (1, 2, 4, 16):
-            grid = 32 * fwd_longest(n, m)
-            got = sorted(4 * it[0] + it[1] for it in (fwd_item(wg, n, m) for wg in range(grid)) if it is not None)
-            assert got == list(range(4 * n)), (n, m)
-
-
-def fwd_item_runs(wg, b):
-    """blend_fwd_wave.h: fwd_wave_item with m == 0 -- the PRODUCT path: one run per XCD, boundaries from the range scan."""
+def fwd_item(wg, b):
+    """blend_fwd_wave.h: fwd_wave_item -- one run per XCD, boundaries from the range scan."""
     x, jj = wg & 7, wg >> 3
     tl, quad = jj >> 2, jj & 3
     start, length = b[x], b[x + 1] - b[x]
@@ -188,8 +165,8 @@ def piece_search_bounds(counts, cap, fix):
 
 
 def test_product_forward_mapping_and_piece_search():
-    """The paths the product takes: m == 0 with the range scan's boundaries, and the piece-granular boundary search of
-    tile_ranges_kernel against the plain searchsorted restatement (bounds_from_model)."""
+    """The paths the product takes: the forward's mapping onto the range scan's boundaries, and the piece-granular
+    boundary search of tile_ranges_kernel against the plain searchsorted restatement (bounds_from_model)."""
     rng = np.random.default_rng(2)
     for n in (1, 7, 8, 255, 6700, 8160, 34680):
         for law in range(3):
@@ -205,7 +182,7 @@ def test_product_forward_mapping_and_piece_search():
             want = [0] + [int(np.searchsorted(8 * cw, k * int(cw[-1]), side="left")) + 1 for k in range(1, 8)] + [n]
             assert b == clamp_runs(want, n), (n, law, b, want)
             grid = 32 * longest_of(b, n)
-            got = sorted(4 * it[0] + it[1] for it in (fwd_item_runs(wg, b) for wg in range(grid)) if it is not None)
+            got = sorted(4 * it[0] + it[1] for it in (fwd_item(wg, b) for wg in range(grid)) if it is not None)
             assert got == list(range(4 * n)), (n, law)
 
 

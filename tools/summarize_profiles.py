@@ -37,7 +37,6 @@ def short(n):
 # the trace and maps to no stage is an ERROR now (stage_of(..., strict=True)).
 STAGE_BY_BASE = {"blend_bwd_wave_kernel": "blend_bwd", "blend_bwd_kernel": "blend_bwd",
                  "blend_fwd_kernel": "blend_fwd", "blend_fwd_x3_kernel": "blend_fwd", "blend_fwd_wave_kernel": "blend_fwd", "blend_fwd_wave_rgb_kernel": "blend_fwd",
-                 "run_bounds_from_walks_kernel": "blend_fwd",
                  "preprocess_fwd_kernel": "preprocess",
                  "tile_sort_kernel": "tile_sort", "tile_sort_wave_kernel": "tile_sort", "reuse_image_state_kernel": "tile_scan", "tile_ranges_kernel": "tile_scan",
                  "geometry_bwd_kernel": "geom_bwd", "unpack_mask_kernel": "geom_bwd"}
