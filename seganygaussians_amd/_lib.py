@@ -32,6 +32,9 @@ EXPORTS = [
     "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
 ]
 MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_scales"]   # include/mi_mask_scales.h
+SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
+MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
+MI_SEGMENT_PRE = {"none": 0, "l2": 1, "eps": 2}
 
 _lib = None
 
@@ -129,6 +132,14 @@ def load():
     L.mi_mask_erode.argtypes = [i, i, i, vp, i, i, vp, vp]
     L.mi_mask_scales.restype = i
     L.mi_mask_scales.argtypes = [i, i, i, vp, vp, C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp]
+    L.mi_segment_scores.restype = i
+    L.mi_segment_scores.argtypes = [i, i, i, i, vp, vp, vp, i, i, vp, vp]
+    L.mi_segment_select.restype = i
+    L.mi_segment_select.argtypes = [i, i, i, i, vp, vp, vp, i, i, f, vp, vp, vp]
+    L.mi_segment_assign.restype = i
+    L.mi_segment_assign.argtypes = [i, i, i, i, vp, vp, vp, i, vp, vp, vp]
+    L.mi_segment_assign_block.restype = i
+    L.mi_segment_assign_block.argtypes = [i]
     _lib = L
     return L
 
