@@ -34,6 +34,8 @@ EXPORTS = [
 MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_scales"]   # include/mi_mask_scales.h
 SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
+PHOTOMETRIC_EXPORTS = ["mi_photo_loss_workspace_bytes", "mi_photo_loss_window", "mi_photo_loss_forward", "mi_photo_loss_backward"]   # include/mi_photometric.h
+MI_PHOTO_L1, MI_PHOTO_SSIM = 1, 2
 MI_SEGMENT_PRE = {"none": 0, "l2": 1, "eps": 2}
 
 _lib = None
@@ -140,6 +142,14 @@ def load():
     L.mi_segment_assign.argtypes = [i, i, i, i, vp, vp, vp, i, vp, vp, vp]
     L.mi_segment_assign_block.restype = i
     L.mi_segment_assign_block.argtypes = [i]
+    L.mi_photo_loss_workspace_bytes.restype = C.c_size_t
+    L.mi_photo_loss_workspace_bytes.argtypes = [i, i, i]
+    L.mi_photo_loss_window.restype = None
+    L.mi_photo_loss_window.argtypes = [C.POINTER(f), C.POINTER(C.c_double)]
+    L.mi_photo_loss_forward.restype = i
+    L.mi_photo_loss_forward.argtypes = [i, i, i, i, vp, vp, C.c_double, i, vp, vp, C.c_size_t, vp, vp]
+    L.mi_photo_loss_backward.restype = i
+    L.mi_photo_loss_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, i, f, f, vp, vp]
     _lib = L
     return L
 
