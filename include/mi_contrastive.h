@@ -22,8 +22,11 @@
  *           g_norm = dL/d rendered_feature_norm, a device scalar, may be NULL = 0), then the 4 S C tap gradients of the rays
  *           are added with float atomics; dL_dgates (N, C) must be zeroed by the caller and receives atomics.
  *
- * All pointers are device pointers, fp32 unless noted, contiguous; `stream` is a hipStream_t.  1 <= C <= 256, N >= 1,
- * S >= 0.  Algorithmic bytes: forward 4 C h w read (+ 4 h w written), backward 4 C h w read + 4 C h w written: three
+ * All pointers are device pointers, fp32 unless noted, contiguous; `stream` is a hipStream_t.  C >= 1, N >= 1, S >= 0; with
+ * rays (S > 0) also C <= 256 (a ray's wave holds four channels per lane) and N <= MI_CONTRASTIVE_LOSS_MAX_SCALES (32, what the
+ * loss below accepts): outside those limits it is mi_contrastive_forward that refuses, so no forward succeeds whose backward
+ * cannot run.  With S = 0 only the dense part runs, and it takes any C and N.  The backward reduces a workgroup's gate
+ * gradients in at most 64 KiB of LDS, in passes of 4096 / C gates.  Algorithmic bytes: forward 4 C h w read (+ 4 h w written), backward 4 C h w read + 4 C h w written: three
  * streams of the feature image (265 MB each at 32 x 1080p); HBM-bound.
  * Returns 0 or an MI_RAST_ERR_* code (mi_rast_last_error() holds the text). */
 #ifndef MI_CONTRASTIVE_H

@@ -23,28 +23,36 @@ def forward(F, idx, cols, normalize_out=True):
     return m
 
 
-def backward(F, idx, cols, g, normalize_out=True):
-    """dL/dF for upstream gradient g [P,C] (float64)."""
+def dmean(F, idx, cols, g, normalize_out=True):
+    """dL/dm_i already divided by k [P,C] (float64): the row every selected neighbour of i receives (pass A of the kernels).
+    idx is any [P,K] map: duplicates in a row, rows without self and unreferenced rows are all allowed."""
     F = np.asarray(F, np.float64)
     g = np.asarray(g, np.float64)
     idx = np.asarray(idx)
     cols = np.asarray(list(cols), np.int64)
-    P, C = F.shape
-    k = len(cols)
-    raw = np.linalg.norm(F, axis=1, keepdims=True)
-    nrm = np.maximum(raw, 1e-12)
-    n = F / nrm
+    n = F / np.maximum(np.linalg.norm(F, axis=1, keepdims=True), 1e-12)
     m = n[idx[:, cols], :].mean(axis=1)
     if normalize_out:
         r = np.linalg.norm(m, axis=1, keepdims=True)
         a = 1.0 / (r + 1e-9)
         mg = (m * g).sum(axis=1, keepdims=True)
         with np.errstate(divide="ignore", invalid="ignore"):
-            b = np.where(r > 0, mg * a * a / r, 0.0)
+            b = np.where(r > 0, mg * a * a / r, 0.0)                     # torch: the norm's subgradient at 0 is 0
         dm = g * a - m * b
     else:
         dm = g
-    dm = dm / k
+    return dm / len(cols)
+
+
+def backward(F, idx, cols, g, normalize_out=True):
+    """dL/dF for upstream gradient g [P,C] (float64)."""
+    F = np.asarray(F, np.float64)
+    idx = np.asarray(idx)
+    cols = np.asarray(list(cols), np.int64)
+    raw = np.linalg.norm(F, axis=1, keepdims=True)
+    nrm = np.maximum(raw, 1e-12)
+    n = F / nrm
+    dm = dmean(F, idx, cols, g, normalize_out)
     dn = np.zeros_like(F)
     for c in cols:                                                       # index_put with accumulation
         np.add.at(dn, idx[:, c], dm)

@@ -23,11 +23,14 @@ constexpr int CT_MAX_CPL = 4;       // channels per lane of a ray's wave: C <= 2
                                     // ~2000 workgroups at 1080p -- 64 slots, 128 bytes apart, summed by the caller
 
 // Source index and upper weight of output index `dst` for bilinear interpolation with align_corners = False
-// (ATen/native/UpSample.h area_pixel_compute_source_index: scale = in / out, src = max(0, (dst + 0.5) scale - 0.5)).
+// (ATen/native/UpSample.h area_pixel_compute_source_index: scale = in / out, src = max(0, scale (dst + 0.5) - 0.5)).  ATen's
+// builds contract that expression into ONE fused multiply-add, on the CPU as on the GPU; this file is compiled with
+// -ffp-contract=off, so the fmaf is spelled out: the unfused form lands one ulp of src (up to 3e-5 of a weight at 1080 rows)
+// away at a few indices of a non-trivial resize (tests/test_contrastive_frontend_edges.py pins the taps to F.interpolate).
 __device__ __forceinline__ void bilinear_tap(int dst, int n_out, int n_in, int& i0, int& i1, float& lam)
 {
     const float scale = (float)n_in / (float)n_out;
-    const float src = fmaxf((dst + 0.5f) * scale - 0.5f, 0.0f);
+    const float src = fmaxf(fmaf(dst + 0.5f, scale, -0.5f), 0.0f);
     i0 = min((int)src, n_in - 1);
     i1 = min(i0 + 1, n_in - 1);
     lam = src - (float)i0;
@@ -158,84 +161,96 @@ __global__ void __launch_bounds__(CT_THREADS) contrastive_bwd_dense_kernel(
 
 // One wave per ray; a workgroup's four rays reduce their gate gradients in LDS before the atomics.  The gates are walked in
 // batches of CT_GB: all of a batch's loads are issued before the first reduction (one memory latency per batch, not per gate).
+// The LDS holds `gates_per_pass` gates per wave (4 waves x gates_per_pass x C floats <= 64 KiB, chosen by the host): N gates
+// take ceil(N / gates_per_pass) passes, each closed by the workgroup's reduction -- one pass whenever N C <= CT_LDS_FLOATS.
 constexpr int CT_GB = 5;
+constexpr int CT_LDS_FLOATS = 4096;   // gate-gradient floats per wave: 4 waves x 4096 x 4 bytes = 64 KiB
 __global__ void __launch_bounds__(CT_THREADS) contrastive_bwd_rays_kernel(
-    int C, int h, int w, int H, int W, int S, const int* __restrict__ ray_yx, int N, const float* __restrict__ gates,
-    const float* __restrict__ out, const float* __restrict__ ray_feat, const float* __restrict__ inv_len,
-    const float* __restrict__ dL_dout, float* __restrict__ dL_drendered, float* __restrict__ dL_dgates)
+    int C, int h, int w, int H, int W, int S, const int* __restrict__ ray_yx, int N, int gates_per_pass,
+    const float* __restrict__ gates, const float* __restrict__ out, const float* __restrict__ ray_feat,
+    const float* __restrict__ inv_len, const float* __restrict__ dL_dout, float* __restrict__ dL_drendered,
+    float* __restrict__ dL_dgates)
 {
-    extern __shared__ float s_dg[];   // [waves][N * C]
+    extern __shared__ float s_dg[];   // [waves][gates_per_pass * C]
     const size_t HW = (size_t)h * w;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int s = (int)blockIdx.x * (CT_THREADS / 64) + wv;
-    float* my_dg = s_dg + (size_t)wv * N * C;
-    for (int i = lane; i < N * C; i += 64) my_dg[i] = 0.f;
-    if (s < S) {
-        int y0, y1, x0, x1;
-        float ly, lx;
-        bilinear_tap(ray_yx[2 * s], H, h, y0, y1, ly);
-        bilinear_tap(ray_yx[2 * s + 1], W, w, x0, x1, lx);
-        float ray[CT_MAX_CPL], dray[CT_MAX_CPL];
+    const int stride = gates_per_pass * C;
+    float* my_dg = s_dg + (size_t)wv * stride;
+    float ray[CT_MAX_CPL], dray[CT_MAX_CPL];
 #pragma unroll
-        for (int k = 0; k < CT_MAX_CPL; k++) {
-            const int c = lane + 64 * k;
-            ray[k] = c < C ? ray_feat[(size_t)s * C + c] : 0.f;
-            dray[k] = 0.f;
-        }
-        for (int n0 = 0; n0 < N; n0 += CT_GB) {
-            float g[CT_GB][CT_MAX_CPL], o[CT_GB][CT_MAX_CPL], gt[CT_GB][CT_MAX_CPL], il[CT_GB], dot[CT_GB];
+    for (int k = 0; k < CT_MAX_CPL; k++) {
+        const int c = lane + 64 * k;
+        ray[k] = (s < S && c < C) ? ray_feat[(size_t)s * C + c] : 0.f;
+        dray[k] = 0.f;
+    }
+    for (int p0 = 0; p0 < N; p0 += gates_per_pass) {   // (uniform over the workgroup: every thread reaches the barriers)
+        const int p1 = min(p0 + gates_per_pass, N);
+        const int span = (p1 - p0) * C;
+        if (p0 > 0) __syncthreads();                   // the previous pass's reduction has read s_dg
+        for (int i = lane; i < span; i += 64) my_dg[i] = 0.f;
+        if (s < S) {
+            for (int n0 = p0; n0 < p1; n0 += CT_GB) {
+                float g[CT_GB][CT_MAX_CPL], o[CT_GB][CT_MAX_CPL], gt[CT_GB][CT_MAX_CPL], il[CT_GB], dot[CT_GB];
 #pragma unroll
-            for (int b = 0; b < CT_GB; b++) {
-                const int n = min(n0 + b, N - 1);
-                il[b] = inv_len[(size_t)n * S + s];
+                for (int b = 0; b < CT_GB; b++) {
+                    const int n = min(n0 + b, p1 - 1);
+                    il[b] = inv_len[(size_t)n * S + s];
 #pragma unroll
-                for (int k = 0; k < CT_MAX_CPL; k++) {
-                    const int c = lane + 64 * k;
-                    const size_t i = ((size_t)n * S + s) * C + c;
-                    g[b][k] = c < C ? dL_dout[i] : 0.f;
-                    o[b][k] = c < C ? out[i] : 0.f;
-                    gt[b][k] = c < C ? gates[(size_t)n * C + c] : 0.f;
+                    for (int k = 0; k < CT_MAX_CPL; k++) {
+                        const int c = lane + 64 * k;
+                        const size_t i = ((size_t)n * S + s) * C + c;
+                        g[b][k] = c < C ? dL_dout[i] : 0.f;
+                        o[b][k] = c < C ? out[i] : 0.f;
+                        gt[b][k] = c < C ? gates[(size_t)n * C + c] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int b = 0; b < CT_GB; b++) {
+                    float d = 0.f;
+#pragma unroll
+                    for (int k = 0; k < CT_MAX_CPL; k++) d = fmaf(g[b][k], o[b][k], d);
+                    dot[b] = wave_sum(d);   // d normalize: (g - o <g, o>) / len over the channels of (n, s)
+                }
+#pragma unroll
+                for (int b = 0; b < CT_GB; b++) {
+                    if (n0 + b >= p1) break;
+#pragma unroll
+                    for (int k = 0; k < CT_MAX_CPL; k++) {
+                        const int c = lane + 64 * k;
+                        if (c < C) {
+                            const float dsc = (g[b][k] - o[b][k] * dot[b]) * il[b];   // d (ray * gate)
+                            dray[k] = fmaf(dsc, gt[b][k], dray[k]);
+                            my_dg[(n0 + b - p0) * C + c] = dsc * ray[k];
+                        }
+                    }
                 }
             }
-#pragma unroll
-            for (int b = 0; b < CT_GB; b++) {
-                float d = 0.f;
-#pragma unroll
-                for (int k = 0; k < CT_MAX_CPL; k++) d = fmaf(g[b][k], o[b][k], d);
-                dot[b] = wave_sum(d);   // d normalize: (g - o <g, o>) / len over the channels of (n, s)
-            }
-#pragma unroll
-            for (int b = 0; b < CT_GB; b++) {
-                if (n0 + b >= N) break;
+            if (p1 == N) {   // every gate has added to dray: the ray's four taps
+                int y0, y1, x0, x1;
+                float ly, lx;
+                bilinear_tap(ray_yx[2 * s], H, h, y0, y1, ly);
+                bilinear_tap(ray_yx[2 * s + 1], W, w, x0, x1, lx);
 #pragma unroll
                 for (int k = 0; k < CT_MAX_CPL; k++) {
                     const int c = lane + 64 * k;
                     if (c < C) {
-                        const float dsc = (g[b][k] - o[b][k] * dot[b]) * il[b];   // d (ray * gate)
-                        dray[k] = fmaf(dsc, gt[b][k], dray[k]);
-                        my_dg[(n0 + b) * C + c] = dsc * ray[k];
+                        float* gp = dL_drendered + (size_t)c * HW;
+                        atomicAdd(&gp[(size_t)y0 * w + x0], dray[k] * (1.f - ly) * (1.f - lx));
+                        atomicAdd(&gp[(size_t)y0 * w + x1], dray[k] * (1.f - ly) * lx);
+                        atomicAdd(&gp[(size_t)y1 * w + x0], dray[k] * ly * (1.f - lx));
+                        atomicAdd(&gp[(size_t)y1 * w + x1], dray[k] * ly * lx);
                     }
                 }
             }
         }
+        __syncthreads();
+        for (int i = threadIdx.x; i < span; i += CT_THREADS) {
+            float t = 0.f;
 #pragma unroll
-        for (int k = 0; k < CT_MAX_CPL; k++) {
-            const int c = lane + 64 * k;
-            if (c < C) {
-                float* gp = dL_drendered + (size_t)c * HW;
-                atomicAdd(&gp[(size_t)y0 * w + x0], dray[k] * (1.f - ly) * (1.f - lx));
-                atomicAdd(&gp[(size_t)y0 * w + x1], dray[k] * (1.f - ly) * lx);
-                atomicAdd(&gp[(size_t)y1 * w + x0], dray[k] * ly * (1.f - lx));
-                atomicAdd(&gp[(size_t)y1 * w + x1], dray[k] * ly * lx);
-            }
+            for (int k = 0; k < CT_THREADS / 64; k++) t += s_dg[(size_t)k * stride + i];
+            if (t != 0.f) atomicAdd(&dL_dgates[(size_t)p0 * C + i], t);
         }
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < N * C; i += CT_THREADS) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < CT_THREADS / 64; k++) t += s_dg[(size_t)k * N * C + i];
-        if (t != 0.f) atomicAdd(&dL_dgates[i], t);
     }
 }
 

@@ -733,6 +733,8 @@ int mi_contrastive_forward(int C, int h, int w, const float* rendered, int H, in
     hipStream_t stream = (hipStream_t)stream_;
     if (C < 1 || h < 1 || w < 1 || H < 1 || W < 1 || S < 0 || N < 1) return fail(MI_RAST_ERR_INVALID, "contrastive: need C, h, w, H, W, N >= 1 and S >= 0");
     if (S > 0 && C > 64 * CT_MAX_CPL) return fail(MI_RAST_ERR_INVALID, "contrastive: at most 256 channels");
+    // what the loss that consumes `out` accepts (cl_check_loss): refused here, before anything is computed, not in the backward
+    if (S > 0 && N > MI_CONTRASTIVE_LOSS_MAX_SCALES) return fail(MI_RAST_ERR_INVALID, "contrastive: at most 32 scales");
     if (!rendered || !inv_norm || !norm_sum || !gates) return fail(MI_RAST_ERR_INVALID, "contrastive: null pointer");
     if (S > 0 && (!ray_yx || !out || !ray_feat || !inv_len)) return fail(MI_RAST_ERR_INVALID, "contrastive: null ray buffers");
     const size_t HW = (size_t)h * w;
@@ -759,8 +761,11 @@ int mi_contrastive_backward(int C, int h, int w, const float* rendered, int H, i
     if (C < 1 || h < 1 || w < 1 || H < 1 || W < 1 || S < 0 || N < 1) return fail(MI_RAST_ERR_INVALID, "contrastive: need C, h, w, H, W, N >= 1 and S >= 0");
     if (!rendered || !inv_norm || !dL_drendered) return fail(MI_RAST_ERR_INVALID, "contrastive: null pointer");
     if (S > 0 && (!ray_yx || !out || !ray_feat || !inv_len || !dL_dout || !gates || !dL_dgates)) return fail(MI_RAST_ERR_INVALID, "contrastive: null ray buffers");
-    const size_t lds = (size_t)(CT_THREADS / 64) * N * C * sizeof(float);
-    if (S > 0 && lds > 64 * 1024) return fail(MI_RAST_ERR_INVALID, "contrastive: N * C too large for the gate-gradient reduction (4 N C floats of LDS)");
+    if (S > 0 && C > 64 * CT_MAX_CPL) return fail(MI_RAST_ERR_INVALID, "contrastive: at most 256 channels");
+    if (S > 0 && N > MI_CONTRASTIVE_LOSS_MAX_SCALES) return fail(MI_RAST_ERR_INVALID, "contrastive: at most 32 scales");
+    // the gate gradients of a workgroup's four rays meet in LDS, at most CT_LDS_FLOATS per wave (64 KiB in all) at a time
+    const int gates_per_pass = S > 0 ? std::min(N, CT_LDS_FLOATS / C) : 0;
+    const size_t lds = (size_t)(CT_THREADS / 64) * gates_per_pass * C * sizeof(float);
     const size_t HW = (size_t)h * w;
     const bool vec = HW % 4 == 0 && ((uintptr_t)rendered % 16) == 0 && ((uintptr_t)inv_norm % 16) == 0 && ((uintptr_t)dL_drendered % 16) == 0;
     const size_t per_block = (size_t)CT_THREADS * (vec ? 4 : 1);
@@ -771,8 +776,8 @@ int mi_contrastive_backward(int C, int h, int w, const float* rendered, int H, i
         hipLaunchKernelGGL(contrastive_bwd_dense_kernel<1>, dim3(dense_blocks), dim3(CT_THREADS), 0, stream, C, h, w, rendered, inv_norm, g_norm, dL_drendered);
     if (S > 0) {
         const uint32_t ray_blocks = (uint32_t)((S + CT_THREADS / 64 - 1) / (CT_THREADS / 64));
-        hipLaunchKernelGGL(contrastive_bwd_rays_kernel, dim3(ray_blocks), dim3(CT_THREADS), lds, stream, C, h, w, H, W, S, ray_yx, N, gates, out,
-                           ray_feat, inv_len, dL_dout, dL_drendered, dL_dgates);
+        hipLaunchKernelGGL(contrastive_bwd_rays_kernel, dim3(ray_blocks), dim3(CT_THREADS), lds, stream, C, h, w, H, W, S, ray_yx, N, gates_per_pass, gates,
+                           out, ray_feat, inv_len, dL_dout, dL_drendered, dL_dgates);
     }
     HIP_TRY(hipGetLastError());
     return MI_RAST_OK;
