@@ -36,6 +36,7 @@ SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign"
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
 PHOTOMETRIC_EXPORTS = ["mi_photo_loss_workspace_bytes", "mi_photo_loss_window", "mi_photo_loss_forward", "mi_photo_loss_backward"]   # include/mi_photometric.h
 MI_PHOTO_L1, MI_PHOTO_SSIM = 1, 2
+ALL_EXPORTS = EXPORTS + MASK_SCALES_EXPORTS + SEGMENT_EXPORTS + PHOTOMETRIC_EXPORTS   # every function the headers in include/ declare
 MI_SEGMENT_PRE = {"none": 0, "l2": 1, "eps": 2}
 
 _lib = None

@@ -8,14 +8,18 @@ from __future__ import annotations
 import os
 import shutil
 import subprocess
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmi_rast.so")
 PROF_LIB_PATH = os.path.join(_HERE, "libmi_rast_prof.so")
 SRC_DIR = os.path.join(_HERE, "csrc")
-SOURCES = ["mi_rast.hip", "common.h", "cull.h", "geometry.h", "binning.h", "knn_smooth.h", "knn.h", "blend_fwd.h", "blend_fwd_split.h", "blend_fwd_wave.h", "blend_fwd_x3.h", "blend_bwd.h", "blend_bwd_shared.h", "blend_bwd_wave.h", "blend_bwd_feat.h", "contrastive.h", "contrastive_loss.h", "mask_scales.h", "segment.h", "photometric.h"]
-HEADER = os.path.join(os.path.dirname(_HERE), "include", "mi_rast.h")
-HEADERS = [os.path.join(os.path.dirname(_HERE), "include", h) for h in ("mi_rast.h", "mi_knn.h", "mi_knn_smooth.h", "mi_contrastive.h", "mi_mask_scales.h", "mi_segment.h", "mi_photometric.h")]
+_INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
+# what a library is built from, read off the directories (is_stale() and source_hash() both go by these): every kernel header and
+# host file (one .hip per public header) in csrc/, every public header in include/
+SOURCES = sorted(f for f in os.listdir(SRC_DIR) if f.endswith((".h", ".hip")))
+HEADERS = [os.path.join(_INCLUDE_DIR, h) for h in sorted(os.listdir(_INCLUDE_DIR)) if h.endswith(".h")]
 
 # -ffp-contract=off is part of the numeric contract: the geometry path that feeds the
 # integer tile/sort results must round every binary32 op separately, like the oracle.
@@ -29,7 +33,7 @@ def source_hash(extra_flags=()) -> str:
     reported next to timings of another (bench.py prints null instead)."""
     import hashlib
     h = hashlib.sha256()
-    for path in sorted([os.path.join(SRC_DIR, f) for f in os.listdir(SRC_DIR) if f.endswith((".h", ".hip"))] + HEADERS):
+    for path in sorted([os.path.join(SRC_DIR, f) for f in SOURCES] + HEADERS):
         h.update(os.path.basename(path).encode())
         h.update(open(path, "rb").read())
     h.update(" ".join(list(HIPCC_FLAGS) + list(extra_flags)).encode())
@@ -56,15 +60,27 @@ def is_stale(lib_path: str = None) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def compile_library(out_path: str, extra_flags=(), verbose: bool = False) -> str:
+    """The one compile path of every library: each csrc/*.hip to an object of its own (HIPCC_FLAGS + extra_flags, at most 16 at a
+    time, in a temporary directory), then one link into <out_path>.tmp, renamed over out_path.  No object is kept between builds."""
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
+    cc = [find_hipcc()] + [f for f in HIPCC_FLAGS if f != "-shared"] + list(extra_flags) + _hash_flag(extra_flags) + ["-c"]
+    units = [s[:-4] for s in SOURCES if s.endswith(".hip")]
+    with tempfile.TemporaryDirectory() as tmp, ThreadPoolExecutor(16) as pool:
+        objs = [os.path.join(tmp, u + ".o") for u in units]
+        list(pool.map(run, [cc + [os.path.join(SRC_DIR, u + ".hip"), "-o", o] for u, o in zip(units, objs)]))
+        run([find_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out_path + ".tmp"] + objs)
+    os.replace(out_path + ".tmp", out_path)
+    return out_path
+
+
 def build_library(force: bool = False, verbose: bool = False) -> str:
     if not force and not is_stale():
         return LIB_PATH
-    cmd = [find_hipcc()] + HIPCC_FLAGS + _hash_flag() + ["-o", LIB_PATH + ".tmp", os.path.join(SRC_DIR, "mi_rast.hip")]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    os.replace(LIB_PATH + ".tmp", LIB_PATH)
-    return LIB_PATH
+    return compile_library(LIB_PATH, verbose=verbose)
 
 
 def build_profiling_library(verbose: bool = False) -> str:
@@ -72,13 +88,7 @@ def build_profiling_library(verbose: bool = False) -> str:
     bf16x3 / RGB) and MI_RAST_F32_BLEND (f32 FMA chain, the tests' bit-exact reference), and per-wave XCD time stamps in the
     blend kernels (mi_rast_xcd_stamps, tools/xcd_stamps.py).  For tests and tools/ only; the product library carries none of
     it.  Select it with MI_RAST_LIB=<path> (seganygaussians_amd/_lib.py)."""
-    cmd = [find_hipcc()] + HIPCC_FLAGS + ["-DMI_RAST_PROFILING"] + _hash_flag(["-DMI_RAST_PROFILING"]) + ["-o", PROF_LIB_PATH + ".tmp",
-                                          os.path.join(SRC_DIR, "mi_rast.hip")]
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.check_call(cmd)
-    os.replace(PROF_LIB_PATH + ".tmp", PROF_LIB_PATH)
-    return PROF_LIB_PATH
+    return compile_library(PROF_LIB_PATH, ["-DMI_RAST_PROFILING"], verbose=verbose)
 
 
 if __name__ == "__main__":

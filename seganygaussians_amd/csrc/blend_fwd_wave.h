@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(64, C == 32 ? FWD_WAVES32 : FWD_WAVES64) blend
     fwd_zero_fill(zfill, blockIdx.x, gridDim.x, (int)(threadIdx.x & 63));   // (every workgroup, also those without an item)
     uint32_t tile, quad;
     if (!fwd_wave_item(blockIdx.x, run_bounds, tile, quad)) return;
-    MI_XCD_STAMP(false);   // (profiling build: per-XCD start / end stamps, common.h)
+    MI_XCD_STAMP(false);   // (profiling build: per-XCD start / end stamps, blend_fwd.h)
     const int lane = threadIdx.x & 63;
     const uint32_t tile_x = tile % horizontal_blocks, tile_y = tile / horizontal_blocks;
     const uint32_t px = tile_x * TILE_X + (quad & 1) * 8 + (lane & 7);

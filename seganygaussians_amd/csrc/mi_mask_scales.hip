@@ -1,0 +1,71 @@
+// mi_mask_scales.hip -- C-ABI implementation of include/mi_mask_scales.h.
+#include "host.h"
+#include "../../include/mi_contrastive.h"   // MI_CONTRASTIVE_LOSS_MAX_MASKS
+#include "../../include/mi_mask_scales.h"
+
+#include "mask_scales.h"   // SAM-mask 3-D scales: erosion and per-mask point spread
+
+using namespace mirast;
+
+namespace {
+int ms_check(int M, int H, int W, const char* what)
+{
+    if (M < 1 || M > MI_CONTRASTIVE_LOSS_MAX_MASKS || H < 1 || W < 1)
+        return fail(MI_RAST_ERR_INVALID, std::string("mask scales: need 1 <= M <= 1024 masks and ") + what + " >= 1");
+    if ((size_t)M * H * ((W + 63) / 64) >= ((size_t)1 << 31)) return fail(MI_RAST_ERR_INVALID, "mask scales: more than 2^31 mask words");
+    return MI_RAST_OK;
+}
+size_t ms_tiles(int H, int W) { return (size_t)((H + MS_TILE_ROWS - 1) / MS_TILE_ROWS) * ((W + 63) / 64); }
+}  // namespace
+
+extern "C" {
+
+size_t mi_mask_scales_workspace_bytes(int M, int H, int W)
+{
+    if (M < 1 || H < 1 || W < 1) return 0;
+    return (size_t)M * ms_tiles(H, W) * MS_STATS * sizeof(double);
+}
+
+int mi_mask_erode(int M, int h, int w, const unsigned long long* packed_in, int H, int W, unsigned long long* packed_out, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = ms_check(M, h, w, "h, w")) return rc;
+    if (int rc = ms_check(M, H, W, "H, W")) return rc;
+    if (!packed_in || !packed_out) return fail(MI_RAST_ERR_INVALID, "mask scales: null pointer");
+    const int Wqi = (w + 63) / 64, Wq = (W + 63) / 64;
+    const size_t in_words = (size_t)M * h * Wqi, words = (size_t)M * H * Wq;
+    if (packed_out < packed_in + in_words && packed_in < packed_out + words)
+        return fail(MI_RAST_ERR_INVALID, "mask scales: the eroded masks must not overlap the input masks");
+    if (h == H && w == W) {
+        hipLaunchKernelGGL(ms_erode_same_kernel, dim3((unsigned)((words + MS_THREADS - 1) / MS_THREADS)), dim3(MS_THREADS), 0, stream,
+                           M, H, W, Wq, (const uint64_t*)packed_in, (uint64_t*)packed_out);
+    } else {
+        // area_pixel_compute_scale (align_corners=False, no scale factor): (float)in / out
+        const float scale_h = (float)h / (float)H, scale_w = (float)w / (float)W;
+        constexpr int wpb = MS_THREADS / 64;
+        hipLaunchKernelGGL(ms_erode_resample_kernel, dim3((unsigned)((words + wpb - 1) / wpb)), dim3(MS_THREADS), 0, stream,
+                           M, h, w, Wqi, (const uint64_t*)packed_in, H, W, Wq, scale_h, scale_w, (uint64_t*)packed_out);
+    }
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
+int mi_mask_scales(int M, int H, int W, const unsigned long long* eroded, const float* depth, double fx, double fy, void* workspace,
+                   size_t workspace_bytes, float* scales, long long* counts, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = ms_check(M, H, W, "H, W")) return rc;
+    if (!eroded || !depth || !workspace || !scales || !counts) return fail(MI_RAST_ERR_INVALID, "mask scales: null pointer");
+    if (!(fx > 0.0) || !(fy > 0.0)) return fail(MI_RAST_ERR_INVALID, "mask scales: need focal lengths fx, fy > 0");
+    if (workspace_bytes < mi_mask_scales_workspace_bytes(M, H, W))
+        return fail(MI_RAST_ERR_INVALID, "mask scales: workspace smaller than mi_mask_scales_workspace_bytes(M, H, W)");
+    const size_t T = ms_tiles(H, W);
+    if (T >= ((size_t)1 << 31)) return fail(MI_RAST_ERR_INVALID, "mask scales: image too large");
+    hipLaunchKernelGGL(ms_moments_kernel, dim3((unsigned)T), dim3(64), 0, stream, M, H, W, (W + 63) / 64, (const uint64_t*)eroded, depth,
+                       fx, fy, (int)T, (double*)workspace);
+    hipLaunchKernelGGL(ms_finalize_kernel, dim3((unsigned)M), dim3(MS_THREADS), 0, stream, (int)T, (const double*)workspace, scales, counts);
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """CPU-side checks of the C-ABI boundary: the HIP library builds for gfx950, loads, and exports every
-symbol include/mi_rast.h declares; host-side helpers agree with the oracle.  No compute calls (no GPU)."""
+symbol the headers in include/ declare; host-side helpers agree with the oracle.  No compute calls (no GPU)."""
 import ctypes
 import os
 import re
@@ -19,12 +19,47 @@ def lib():
 
 
 def test_header_symbols_exported(lib):
-    hdr = "".join(open(os.path.join(ROOT, "include", h)).read() for h in ("mi_rast.h", "mi_knn_smooth.h", "mi_knn.h", "mi_contrastive.h"))
-    declared = set(re.findall(r"\b(mi_(?:rast|knn|contrastive)_[a-z_0-9]+)\s*\(", hdr)) - {"mi_rast_resize_fn", "mi_rast_last_error"} | {"mi_rast_last_error"}
-    assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
+    """Every function that a header in include/ declares is listed in _lib.ALL_EXPORTS and resolves in the library, and nothing else
+    is listed."""
+    hdr = "".join(open(h).read() for h in build.HEADERS)
+    declared = set(re.findall(r"\b(mi_[a-z_0-9]+)\s*\(", hdr)) - {"mi_rast_resize_fn"}
+    assert len(build.HEADERS) == 7 and len(_lib.ALL_EXPORTS) == len(set(_lib.ALL_EXPORTS))
+    assert declared == set(_lib.ALL_EXPORTS), declared ^ set(_lib.ALL_EXPORTS)
     for name in declared:
         assert hasattr(lib, name), name
         assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
+
+
+# one call per host file of csrc/ that is refused for its arguments before any HIP call (the pointers are never read), and its message
+REFUSED = [
+    ("mi_rast_forward_reuse", (0, 3, 0, None, 16, 16) + (None,) * 6 + (0,) + (None,) * 4 + (0,) + (None,) * 3, "P, width and height must be positive"),
+    ("mi_knn_query", (4, 8, 4, 8, 5, 0, 8, 8, None), "knn: K must be one of 1, 3, 4, 8, 16, 32"),
+    ("mi_knn_smooth_forward", (4, 48, 8, 8, 0xFF, 8, 8, 0, None), "knn_smooth: need C in {32, 64} and 1 <= K <= 32"),
+    ("mi_contrastive_pack_masks", (0, 4, 4, 8, 8, None), "contrastive loss: need 1 <= M <= 1024 masks and H, W >= 1"),
+    ("mi_mask_erode", (0, 4, 4, 8, 4, 4, 4096, None), "mask scales: need 1 <= M <= 1024 masks and h, w >= 1"),
+    ("mi_segment_scores", (2, 4, 4, 1, 8, 8, None, 0, 1, 8, None), "segment: layout must be MI_SEGMENT_IMAGE or MI_SEGMENT_POINTS"),
+    ("mi_photo_loss_forward", (0, 3, 4, 4, 8, 8, 0.2, 3, None, 8, 1 << 20, 8, None), "photometric: need images, planes, H, W >= 1"),
+]
+
+
+def test_last_error_is_one_per_thread_for_every_host_file(lib):
+    """The host side is one translation unit per public header: what any of them refuses must be what mi_rast_last_error()
+    (mi_rast.hip) returns -- one thread-local string for the whole library, not one per file."""
+    import threading
+    for name, args, msg in REFUSED:
+        assert getattr(lib, name)(*args) != 0, name
+        assert _lib.last_error() == msg, name
+    mine, seen = _lib.last_error(), []
+
+    def other():
+        seen.append(_lib.last_error())   # a new thread: no message yet
+        seen.append(lib.mi_knn_query(4, 8, 4, 8, 5, 0, 8, 8, None))
+        seen.append(_lib.last_error())
+    t = threading.Thread(target=other)
+    t.start()
+    t.join()
+    assert seen[0] == "" and seen[1] != 0 and seen[2] == REFUSED[1][2]
+    assert _lib.last_error() == mine == REFUSED[-1][2]   # the other thread's message is not visible here
 
 
 def test_no_torch_types_in_abi():

@@ -4,7 +4,6 @@
    python tools/build_variants.py base=-DMI_BWD_HYBRID_EXP=0,-DMI_BWD_SEPMOM=0 hyb=-DMI_BWD_SEPMOM=0
 """
 import os
-import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 
@@ -16,12 +15,9 @@ from seganygaussians_amd import build as b  # noqa: E402
 def one(spec):
     name, _, flags = spec.partition("=")
     out = os.path.join(root, "seganygaussians_amd", f"libmi_rast_{name}.so")
-    extra = [f for f in flags.split(",") if f]
-    cmd = [b.find_hipcc()] + b.HIPCC_FLAGS + extra + b._hash_flag(extra) + ["-o", out, os.path.join(b.SRC_DIR, "mi_rast.hip")]
-    subprocess.check_call(cmd)
-    return out
+    return b.compile_library(out, [f for f in flags.split(",") if f])
 
 
-with ThreadPoolExecutor(4) as ex:
+with ThreadPoolExecutor(2) as ex:   # (each build compiles its host files side by side: seganygaussians_amd/build.py)
     for p in ex.map(one, sys.argv[1:]):
         print("built", p)

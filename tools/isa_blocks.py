@@ -1,6 +1,6 @@
-"""Per-basic-block instruction mix of one kernel of csrc/mi_rast.hip as hipcc compiles it for gfx950 (no GPU needed).
+"""Per-basic-block instruction mix of one kernel of a host file of csrc/ (--file NAME, default mi_rast.hip) as hipcc compiles it for gfx950 (no GPU needed).
 
-   python tools/isa_blocks.py <kernel substring> [<template substring>] [--min N] [--dump LABEL] [-D...]
+   python tools/isa_blocks.py <kernel substring> [<template substring>] [--file NAME] [--min N] [--dump LABEL] [-D...]
 
 Prints one line per basic block with >= N instructions: VALU / transcendental / SALU / MFMA / LDS / global loads /
 stores / atomics / s_waitcnt, and marks blocks that are targets of a backward branch (loop heads).  --dump LABEL prints
@@ -12,7 +12,7 @@ import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 args = [a for a in sys.argv[1:]]
-minn, dump, subs, defs = 20, None, [], []
+minn, dump, subs, defs, fname = 20, None, [], [], "mi_rast.hip"
 i = 0
 while i < len(args):
     a = args[i]
@@ -20,12 +20,14 @@ while i < len(args):
         minn = int(args[i + 1]); i += 2; continue
     if a == "--dump":
         dump = args[i + 1]; i += 2; continue
+    if a == "--file":
+        fname = args[i + 1]; i += 2; continue
     if a.startswith("-D"):
         defs.append(a); i += 1; continue
     subs.append(a); i += 1
 tag = "_".join(d[2:] for d in defs) or "base"
-out_s = f"/tmp/isa_blocks_{tag}.s"
-src = os.path.join(root, "seganygaussians_amd/csrc/mi_rast.hip")
+out_s = f"/tmp/isa_blocks_{os.path.splitext(fname)[0]}_{tag}.s"
+src = os.path.join(root, "seganygaussians_amd/csrc", fname)
 deps = [os.path.join(root, "seganygaussians_amd/csrc", f) for f in os.listdir(os.path.join(root, "seganygaussians_amd/csrc"))]
 if not os.path.exists(out_s) or any(os.path.getmtime(d) > os.path.getmtime(out_s) for d in deps):
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",

@@ -1,12 +1,14 @@
-"""Resource usage (VGPRs, spills, LDS, occupancy) of every kernel of csrc/mi_rast.hip as hipcc reports it for gfx950.
-   python tools/kres.py [substring] [-DMI_RAST_PROFILING]"""
+"""Resource usage (VGPRs, spills, LDS, occupancy) of every kernel of one host file of csrc/ (--file=NAME, default mi_rast.hip) as hipcc
+reports it for gfx950.
+   python tools/kres.py [substring] [--file=mi_knn.hip] [-DMI_RAST_PROFILING]"""
 import re, subprocess, sys, os
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flt = [a for a in sys.argv[1:] if not a.startswith("-")]
-extra = [a for a in sys.argv[1:] if a.startswith("-")]
+extra = [a for a in sys.argv[1:] if a.startswith("-") and not a.startswith("--file=")]
+src = ([a[7:] for a in sys.argv[1:] if a.startswith("--file=")] or ["mi_rast.hip"])[-1]
 cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-munsafe-fp-atomics",
        "-fno-slp-vectorize", "--cuda-device-only", "-c", "-Rpass-analysis=kernel-resource-usage",
-       os.path.join(root, "seganygaussians_amd/csrc/mi_rast.hip"), "-o", "/tmp/kres.o"] + extra
+       os.path.join(root, "seganygaussians_amd/csrc", src), "-o", "/tmp/kres.o"] + extra
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur, d = None, {}
 for l in out.splitlines():
