@@ -18,6 +18,8 @@ from __future__ import annotations
 
 import torch
 
+from ._ffi import check, ptr, stream_ptr
+
 
 def _src_index(n_out: int, n_in: int, device, dtype):
     """Source coordinate, lower tap, upper tap and upper weight for every output index: the area_pixel_compute_*
@@ -58,10 +60,6 @@ def sample_scale_conditioned_features(rendered_features: torch.Tensor, out_hw, s
 # The HIP path (include/mi_contrastive.h, csrc/contrastive.h): regulariser + rays, forward and backward
 # ---------------------------------------------------------------------------------------------------------------------
 
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
 class _ContrastiveFrontEnd(torch.autograd.Function):
     """(rendered (C,h,w), gates (N,C)) -> (out (N,S,C), rendered_feature_norm ()) through mi_contrastive_forward / _backward."""
 
@@ -90,11 +88,9 @@ class _ContrastiveFrontEnd(torch.autograd.Function):
         inv_norm = torch.empty((h * w,), device=dev, dtype=torch.float32)
         norm_sum = torch.zeros((64 * 16,), device=dev, dtype=torch.float64)   # MI_CONTRASTIVE_NORM_SLOTS partial sums, one per 128-byte line
         with torch.cuda.device(dev):   # the launch pairs the stream with the CURRENT device
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = L.mi_contrastive_forward(C, h, w, rendered.data_ptr(), int(H), int(W), S, _ptr(ray_yx), N, gates_c.data_ptr(),
-                                          _ptr(out), _ptr(ray_feat), _ptr(inv_len), inv_norm.data_ptr(), norm_sum.data_ptr(), stream)
-        if rc != 0:
-            raise RuntimeError(_lib.last_error())
+            rc = L.mi_contrastive_forward(C, h, w, rendered.data_ptr(), int(H), int(W), S, ptr(ray_yx), N, gates_c.data_ptr(),
+                                          ptr(out), ptr(ray_feat), ptr(inv_len), inv_norm.data_ptr(), norm_sum.data_ptr(), stream_ptr(dev))
+        check(rc)
         ctx.save_for_backward(rendered, gates_c, ray_yx, out, ray_feat, inv_len, inv_norm)
         ctx.dims = (C, h, w, int(H), int(W), S, N)
         return out, (norm_sum.sum() / float(h * w)).float()
@@ -113,12 +109,10 @@ class _ContrastiveFrontEnd(torch.autograd.Function):
             d_out_c = torch.zeros((N, S, C), device=dev, dtype=torch.float32)
         g = None if d_norm is None else d_norm.reshape(1).contiguous().float()
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            rc = L.mi_contrastive_backward(C, h, w, rendered.data_ptr(), H, W, S, _ptr(ray_yx), N, gates_c.data_ptr(), _ptr(out),
-                                           _ptr(ray_feat), _ptr(inv_len), inv_norm.data_ptr(), _ptr(d_out_c), _ptr(g),
-                                           d_rendered.data_ptr(), d_gates.data_ptr(), stream)
-        if rc != 0:
-            raise RuntimeError(_lib.last_error())
+            rc = L.mi_contrastive_backward(C, h, w, rendered.data_ptr(), H, W, S, ptr(ray_yx), N, gates_c.data_ptr(), ptr(out),
+                                           ptr(ray_feat), ptr(inv_len), inv_norm.data_ptr(), ptr(d_out_c), ptr(g),
+                                           d_rendered.data_ptr(), d_gates.data_ptr(), stream_ptr(dev))
+        check(rc)
         # gradients in the dtype (and, for the gates, on the device) the inputs came in
         return d_rendered.to(ctx.in_dtypes[0]), d_gates.to(ctx.in_dtypes[1]), None, None, None
 

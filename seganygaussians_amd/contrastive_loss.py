@@ -21,25 +21,13 @@ from dataclasses import dataclass
 
 import torch
 
+from ._ffi import check, ptr, stream_ptr
+
 MAX_MASKS = 1024     # MI_CONTRASTIVE_LOSS_MAX_MASKS
 MAX_SCALES = 32      # MI_CONTRASTIVE_LOSS_MAX_SCALES
 MAX_CHANNELS = 256
 _ROW_STATS = 8       # CL_ROW_STATS (csrc/contrastive_loss.h)
 _ACC_HEAD = 5        # class counts (3), max a, ~min a; then the M mask areas
-
-
-def _ptr(t):
-    return None if t is None or t.numel() == 0 else t.data_ptr()
-
-
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
-def _check(rc):
-    from . import _lib
-    if rc != 0:
-        raise RuntimeError(_lib.last_error())
 
 
 @dataclass
@@ -71,7 +59,7 @@ def pack_sam_masks(masks: torch.Tensor, device=None) -> PackedSamMasks:
     src = masks.to(dev).contiguous()
     words = torch.empty((M, H, (W + 63) // 64), device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
-        _check(L.mi_contrastive_pack_masks(M, H, W, src.data_ptr(), words.data_ptr(), _stream(dev)))
+        check(L.mi_contrastive_pack_masks(M, H, W, src.data_ptr(), words.data_ptr(), stream_ptr(dev)))
     return PackedSamMasks(words, (M, H, W))
 
 
@@ -178,17 +166,17 @@ def sample_contrastive_targets(masks, mask_scales: torch.Tensor, upper_bound_sca
     sampled_ray = torch.empty((H, W), device=dev, dtype=torch.bool)
     ray_rand_dev = ray_rand.to(dev)
     with torch.cuda.device(dev):
-        _check(L.mi_contrastive_cover(M, H, W, packed.words.data_ptr(), ray_rand_dev.data_ptr(), float(torch.tensor(rate, dtype=torch.float32)),
-                                      sampled_ray.data_ptr(), acc.data_ptr(), _stream(dev)))
+        check(L.mi_contrastive_cover(M, H, W, packed.words.data_ptr(), ray_rand_dev.data_ptr(), float(torch.tensor(rate, dtype=torch.float32)),
+                                     sampled_ray.data_ptr(), acc.data_ptr(), stream_ptr(dev)))
     ray_yx = torch.nonzero(sampled_ray).to(torch.int32).contiguous()                      # row-major; host sync 2 of 2
     S, Wd = int(ray_yx.shape[0]), (M + 63) // 64
     scale_args = torch.stack([index.to(torch.int32), upper.to(torch.int32)]).to(dev)
     gt = torch.empty((S, N, Wd), device=dev, dtype=torch.int64)
     mean_size = torch.empty((S,), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _check(L.mi_contrastive_targets(M, H, W, packed.words.data_ptr(), sort_idx.data_ptr(), S, _ptr(ray_yx), N,
-                                        scale_args[0].data_ptr(), scale_args[1].data_ptr(), _ptr(gt), _ptr(mean_size), acc.data_ptr(),
-                                        _stream(dev)))
+        check(L.mi_contrastive_targets(M, H, W, packed.words.data_ptr(), sort_idx.data_ptr(), S, ptr(ray_yx), N,
+                                       scale_args[0].data_ptr(), scale_args[1].data_ptr(), ptr(gt), ptr(mean_size), acc.data_ptr(),
+                                       stream_ptr(dev)))
     return ContrastiveTargets(sampled_ray, ray_yx, sampled_scales.to(dev), index, upper, M, gt, mean_size, acc)
 
 
@@ -213,8 +201,8 @@ class _PairLoss(torch.autograd.Function):
         dev = feats.device
         partials = torch.empty((S, _ROW_STATS), device=dev, dtype=torch.float64)
         with torch.cuda.device(dev):
-            _check(L.mi_contrastive_loss_forward(S, N, C, tg.num_masks, _ptr(feats), _ptr(tg.gt), _ptr(tg.mean_size), tg.acc.data_ptr(),
-                                                 _ptr(rand), _ptr(partials), out_f32.data_ptr(), out_i64.data_ptr(), _stream(dev)))
+            check(L.mi_contrastive_loss_forward(S, N, C, tg.num_masks, ptr(feats), ptr(tg.gt), ptr(tg.mean_size), tg.acc.data_ptr(),
+                                                ptr(rand), ptr(partials), out_f32.data_ptr(), out_i64.data_ptr(), stream_ptr(dev)))
         ctx.tg = tg
         ctx.save_for_backward(feats, rand, out_i64)
         return out_f32[0].clone()
@@ -230,8 +218,8 @@ class _PairLoss(torch.autograd.Function):
         d_feats = torch.empty_like(feats)
         g = g.reshape(1).to(dev, torch.float32).contiguous()
         with torch.cuda.device(dev):
-            _check(L.mi_contrastive_loss_backward(S, N, C, tg.num_masks, _ptr(feats), _ptr(tg.gt), _ptr(tg.mean_size), tg.acc.data_ptr(),
-                                                  _ptr(rand), out_i64.data_ptr(), g.data_ptr(), _ptr(d_feats), _stream(dev)))
+            check(L.mi_contrastive_loss_backward(S, N, C, tg.num_masks, ptr(feats), ptr(tg.gt), ptr(tg.mean_size), tg.acc.data_ptr(),
+                                                 ptr(rand), out_i64.data_ptr(), g.data_ptr(), ptr(d_feats), stream_ptr(dev)))
         return d_feats, None, None, None, None
 
 

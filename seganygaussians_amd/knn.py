@@ -15,6 +15,7 @@ from typing import NamedTuple, Optional
 import torch
 
 from . import _lib
+from ._ffi import check, stream_ptr
 
 
 class _KNN(NamedTuple):   # pytorch3d.ops.knn._KNN
@@ -24,11 +25,6 @@ class _KNN(NamedTuple):   # pytorch3d.ops.knn._KNN
 
 
 _SUPPORTED_K = (1, 3, 4, 8, 16, 32)
-
-
-def _check(rc):
-    if rc != 0:
-        raise RuntimeError(_lib.last_error())
 
 
 def _prep(x: torch.Tensor, name: str) -> torch.Tensor:
@@ -49,8 +45,7 @@ class KnnIndex:
         nbytes = int(L.mi_knn_workspace_bytes(self.M))
         self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=ref.device)
         with torch.cuda.device(ref.device):
-            _check(L.mi_knn_build(self.M, ref.data_ptr(), self.workspace.data_ptr(), nbytes,
-                                  torch.cuda.current_stream(ref.device).cuda_stream))
+            check(L.mi_knn_build(self.M, ref.data_ptr(), self.workspace.data_ptr(), nbytes, stream_ptr(ref.device)))
         self._ref = ref   # not needed by the index; kept so that query(None) can report shapes
 
     def query(self, query: Optional[torch.Tensor], K: int, exclude_self: bool = False):
@@ -70,9 +65,8 @@ class KnnIndex:
         idx = torch.empty((rows, kt), dtype=torch.int64, device=self.device)
         d2 = torch.empty((rows, kt), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _check(L.mi_knn_query(rows, None if q is None else q.data_ptr(), self.M, self.workspace.data_ptr(), kt,
-                                  int(bool(exclude_self)), idx.data_ptr(), d2.data_ptr(),
-                                  torch.cuda.current_stream(self.device).cuda_stream))
+            check(L.mi_knn_query(rows, None if q is None else q.data_ptr(), self.M, self.workspace.data_ptr(), kt,
+                                 int(bool(exclude_self)), idx.data_ptr(), d2.data_ptr(), stream_ptr(self.device)))
         return (idx[:, :K].contiguous(), d2[:, :K].contiguous()) if kt != K else (idx, d2)
 
 
@@ -104,6 +98,5 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     nbytes = int(L.mi_knn_workspace_bytes(P))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=pts.device)
     with torch.cuda.device(pts.device):
-        _check(L.mi_knn_mean_dist2(P, pts.data_ptr(), ws.data_ptr(), nbytes, out.data_ptr(),
-                                   torch.cuda.current_stream(pts.device).cuda_stream))
+        check(L.mi_knn_mean_dist2(P, pts.data_ptr(), ws.data_ptr(), nbytes, out.data_ptr(), stream_ptr(pts.device)))
     return out

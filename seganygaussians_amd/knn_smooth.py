@@ -20,7 +20,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .rasterizer import _check, _dev_ptr, _stream_ptr
+from ._ffi import check, dev_ptr, stream_ptr
 
 
 FUSED_MAX_K = 32   # neighbours per row the fused kernels handle (include/mi_knn_smooth.h)
@@ -81,9 +81,9 @@ class _KnnSmooth(torch.autograd.Function):
         f = features.contiguous().float()
         out = torch.empty_like(f)
         with torch.cuda.device(dev):
-            rc = L.mi_knn_smooth_forward(P, C, nmap.K, nmap.idx.data_ptr(), sel_mask, _dev_ptr(f, "features", dev),
-                                         out.data_ptr(), int(bool(normalize_out)), _stream_ptr(dev))
-        _check(rc)
+            rc = L.mi_knn_smooth_forward(P, C, nmap.K, nmap.idx.data_ptr(), sel_mask, dev_ptr(f, "features", dev),
+                                         out.data_ptr(), int(bool(normalize_out)), stream_ptr(dev))
+        check(rc)
         ctx.save_for_backward(f)
         ctx.nmap, ctx.sel_mask, ctx.normalize_out = nmap, sel_mask, bool(normalize_out)
         return out
@@ -101,9 +101,9 @@ class _KnnSmooth(torch.autograd.Function):
         with torch.cuda.device(dev):
             rc = L.mi_knn_smooth_backward(P, C, nmap.K, nmap.idx.data_ptr(), nmap.inv_offsets.data_ptr(),
                                           nmap.inv_entries.data_ptr(), ctx.sel_mask, f.data_ptr(),
-                                          _dev_ptr(g, "grad", dev), dmean.data_ptr(), dF.data_ptr(),
-                                          int(ctx.normalize_out), _stream_ptr(dev))
-        _check(rc)
+                                          dev_ptr(g, "grad", dev), dmean.data_ptr(), dF.data_ptr(),
+                                          int(ctx.normalize_out), stream_ptr(dev))
+        check(rc)
         return dF, None, None, None
 
 

@@ -17,7 +17,8 @@ import math
 
 import torch
 
-from .contrastive_loss import MAX_MASKS, PackedSamMasks, _check, _stream, pack_sam_masks
+from ._ffi import check, stream_ptr
+from .contrastive_loss import MAX_MASKS, PackedSamMasks, pack_sam_masks
 
 
 def _as_packed(masks, dev, who: str) -> PackedSamMasks:
@@ -62,7 +63,7 @@ def _erode(packed: PackedSamMasks, H: int, W: int) -> PackedSamMasks:
         raise ValueError("erode_sam_masks: more than 2^31 mask words")
     out = torch.empty((M, H, (W + 63) // 64), device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
-        _check(L.mi_mask_erode(M, h, w, packed.words.data_ptr(), H, W, out.data_ptr(), _stream(dev)))
+        check(L.mi_mask_erode(M, h, w, packed.words.data_ptr(), H, W, out.data_ptr(), stream_ptr(dev)))
     return PackedSamMasks(out, (M, H, W))
 
 
@@ -118,6 +119,6 @@ def sam_mask_scales(depth: torch.Tensor, masks, fovx: float, fovy: float, return
     scales = torch.empty((M,), device=dev, dtype=torch.float32)
     counts = torch.empty((M,), device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
-        _check(L.mi_mask_scales(M, H, W, eroded.words.data_ptr(), depth.data_ptr(), fx, fy, ws.data_ptr(), ws.numel(),
-                                scales.data_ptr(), counts.data_ptr(), _stream(dev)))
+        check(L.mi_mask_scales(M, H, W, eroded.words.data_ptr(), depth.data_ptr(), fx, fy, ws.data_ptr(), ws.numel(),
+                               scales.data_ptr(), counts.data_ptr(), stream_ptr(dev)))
     return (scales, counts) if return_counts else scales

@@ -18,7 +18,7 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
-from .contrastive_loss import _check, _stream
+from ._ffi import check, stream_ptr
 
 WINDOW_SIZE = 11
 TILE_H, TILE_W = 32, 64       # MI_PHOTO_TILE_H, MI_PHOTO_TILE_W (include/mi_photometric.h)
@@ -60,8 +60,8 @@ def _forward(image, gt, dims, lambda_dssim: float, parts: int, want_maps: bool):
     maps = torch.empty((3, B * C, H, W), device=dev, dtype=torch.float32) if want_maps else None
     ws = torch.empty((L.mi_photo_loss_workspace_bytes(B * C, H, W),), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
-        _check(L.mi_photo_loss_forward(B, C, H, W, image.data_ptr(), gt.data_ptr(), float(lambda_dssim), parts,
-                                       None if maps is None else maps.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream(dev)))
+        check(L.mi_photo_loss_forward(B, C, H, W, image.data_ptr(), gt.data_ptr(), float(lambda_dssim), parts,
+                                      None if maps is None else maps.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr(), stream_ptr(dev)))
     return out, maps
 
 
@@ -73,8 +73,8 @@ def _backward(image, gt, maps, dims, grad_out, per_image: bool, w_l1: float, w_s
     grad = torch.empty(image.shape, device=dev, dtype=torch.float32)
     grad_out = grad_out.to(torch.float32).contiguous()
     with torch.cuda.device(dev):
-        _check(L.mi_photo_loss_backward(B, C, H, W, image.data_ptr(), gt.data_ptr(), None if maps is None else maps.data_ptr(),
-                                        grad_out.data_ptr(), 1 if per_image else 0, w_l1, w_ssim, grad.data_ptr(), _stream(dev)))
+        check(L.mi_photo_loss_backward(B, C, H, W, image.data_ptr(), gt.data_ptr(), None if maps is None else maps.data_ptr(),
+                                       grad_out.data_ptr(), 1 if per_image else 0, w_l1, w_ssim, grad.data_ptr(), stream_ptr(dev)))
     return grad
 
 

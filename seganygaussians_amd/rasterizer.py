@@ -17,6 +17,7 @@ CPU fallback: missing library or non-GPU tensors raise.
 from __future__ import annotations
 
 import contextlib
+import math
 import os
 import ctypes as C
 import threading
@@ -26,6 +27,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._ffi import check, contig, dev_ptr, stream_ptr
+from .geometry_cache import GeometryCache, disable_geometry_cache, enable_geometry_cache, geometry_cache  # noqa: F401  (re-exported)
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -49,27 +52,6 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
-# --------------------------------------------------------------------------------------------------
-# C-ABI call helpers (the "_C" layer)
-# --------------------------------------------------------------------------------------------------
-
-def _dev_ptr(t, name, device=None, dtype=torch.float32):
-    """Empty tensor -> NULL (reference convention, CF/.../__init__.py:196-206 + `!= nullptr` branches)."""
-    if t is None or t.numel() == 0:
-        return None
-    if not t.is_cuda:
-        raise RuntimeError(f"{name} must be a GPU tensor (got {t.device}); the MI355X rasterizer has no CPU path")
-    if t.dtype != dtype:
-        raise RuntimeError(f"{name} must be {dtype} (got {t.dtype})")
-    if device is not None and t.device != device:
-        raise RuntimeError(f"{name} is on {t.device}, expected {device}")
-    return t.data_ptr()
-
-
-def _contig(t):
-    return t if (t is None or t.numel() == 0) else t.contiguous()
-
-
 class _Resizer:
     """Replacement for resizeFunctional (CF/rasterize_points.cu:27-33): a growable torch uint8 buffer
     handed to the library as a C callback."""
@@ -85,15 +67,6 @@ class _Resizer:
             return self.tensor.data_ptr()
         except Exception:  # allocation failure -> NULL -> MI_RAST_ERR_ALLOC
             return None
-
-
-def _check(rc):
-    if rc != 0:
-        raise RuntimeError(_lib.last_error())
-
-
-def _stream_ptr(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 # Per-call options of the native forward (include/mi_rast.h: `flags`, `features_ready_event`).  The C library keeps no
@@ -134,147 +107,36 @@ def forward_flags(full_lists=None, f32_blend=None, no_cull=None, fast_exp=None, 
         _opts.flags = prev
 
 
-# --------------------------------------------------------------------------------------------------
-# frozen-geometry reuse (opt-in; an extension: the reference recomputes everything per call)
-# --------------------------------------------------------------------------------------------------
-class GeometryCache:
-    """Per-camera cache of what the geometry-only stages of a forward produce (preprocess, binning, per-tile sort): the geometry
-    buffer, the blend lists, the tile ranges + XCD run boundaries, radii and num_rendered.  A later forward of the SAME geometry
-    from the SAME camera runs the blend stage alone (include/mi_rast.h: mi_rast_forward_reuse).  Meant for SAGA's contrastive
-    feature training, which optimises the feature rows only (scene/gaussian_model_ff.py:154-162) and revisits each of ~200 cameras
-    ~50 times (train_contrastive_feature.py:231).
+class ForwardNotes:
+    """What a native forward tells the backward of ITS buffers, left on the geometry buffer as `.mi_notes`: the MI_RAST_* flags it
+    ran with (the backward re-takes the forward's decisions: it needs the same ones) and, after a forward with prezero, who may
+    skip the backward's fills.  `prezero` is the zero-filled (P, channels) tensor that becomes dL_dcolors, `pack_zeroed` says that
+    the packed field gradients inside the geometry buffer are zero as well.  `epoch` is the epoch cell of the GeometryCache entry
+    this forward filled: a hit of that view shares the geometry buffer's scratch and bumps the cell."""
+    __slots__ = ("flags", "prezero", "pack_zeroed", "epoch", "epoch_seen")
 
-    The key is CONTENT: 64-bit fingerprints (mi_rast_fingerprint) of means3D, opacities, scales, rotations, cov3D_precomp, shs (when
-    they colour the Gaussians), view / projection matrix and camera position, next to the scalar settings.  The reference's
-    renderer passes activation OUTPUTS (gaussian_renderer/__init__.py:337-348: pc.get_opacity, get_scaling, get_rotation), new
-    tensors per call, so storage identity alone would never hit -- and a freed tensor's address can be handed to another one.  A
-    fingerprint is memoised per tensor OBJECT (weak reference), version counter, storage (weak reference) and data_ptr(): a
-    parameter or camera tensor that is passed again unchanged costs nothing, any in-place change (`means3D.add_(...)`, an optimizer
-    step on a geometry tensor) bumps `_version`, and rebinding (`p.data = new`, which keeps the object and the version) replaces the
-    storage; either gets a new fingerprint and misses.  Writes through `.data` that keep the storage (`p.data.copy_(...)`,
-    `p.data[:] = ...`) change neither and CANNOT be seen: call `clear()` after them.  Tensors seen for the first time are
-    fingerprinted by one kernel, behind which the calling thread waits for the stream.
+    def __init__(self, flags, prezero=None, pack_zeroed=False, epoch=None):
+        self.flags, self.prezero, self.pack_zeroed = int(flags), prezero, bool(pack_zeroed)
+        self.epoch, self.epoch_seen = epoch, (None if epoch is None else epoch[0])
 
-    Bytes kept per view: the geometry buffer (139 bytes per Gaussian), 4 bytes per blend-list entry, 8 bytes per tile, radii (4 bytes
-    per Gaussian).  Least recently used views are dropped beyond `max_bytes`.
+    @classmethod
+    def for_hit(cls, flags, prezero=None):
+        """A forward that reused a cached view: the scratch is shared between the forwards of the view, so its backward fills it."""
+        return cls(flags, prezero, pack_zeroed=False)
 
-    The cached buffers are SHARED between the forwards of a view, the packed-gradient scratch of the geometry buffer included.  Each
-    entry carries an epoch that every hit bumps: the miss forward's pre-zeroed scratch is taken by its backward only while no hit of
-    that view came in between (otherwise the backward zero-fills it itself, as a hit's backward always does).  So any interleaving
-    of forwards and backwards of cached views on one stream -- several renders of a view in one loss, no-grad renders between a
-    forward and its backward, retained graphs -- gives the uncached results (tests/test_geometry_cache_edges.py).  Two backward
-    passes of the same cached view must not run at the same time on different streams.  `debug=True` forwards and the full-list /
-    verify modes of the tests are never cached."""
-
-    def __init__(self, max_bytes=64 << 30):
-        import collections
-        self.max_bytes = int(max_bytes)
-        self.enabled = True
-        self.entries = collections.OrderedDict()
-        self.bytes = 0
-        self.hits = self.misses = 0
-        self._memo = {}          # id(tensor) -> (weakref, _version, storage weakref, data_ptr, fingerprint)
-        self.lock = threading.Lock()
-
-    def stats(self):
-        n = self.hits + self.misses
-        return {"hits": self.hits, "misses": self.misses, "hit_rate": (self.hits / n) if n else 0.0, "views": len(self.entries),
-                "bytes_cached": self.bytes}
-
-    def clear(self):
-        with self.lock:
-            self.entries.clear()
-            self._memo.clear()
-            self.bytes = 0
-            self.hits = self.misses = 0
-
-    def fingerprints(self, tensors, dev):
-        """One 64-bit content fingerprint per tensor (None for an absent one); memoised per (tensor object, version, storage,
-        data_ptr).  The caller has checked that every tensor is a float32 GPU tensor."""
-        import weakref
-        out = [None] * len(tensors)
-        todo = []
-        for k, t in enumerate(tensors):
-            if t is None or t.numel() == 0:
-                continue
-            m = self._memo.get(id(t))
-            if (m is not None and m[0]() is t and m[1] == t._version and m[2]() is t.untyped_storage()
-                    and m[3] == t.data_ptr()):
-                out[k] = m[4]
-            else:
-                todo.append(k)
-        for g0 in range(0, len(todo), 8):
-            grp = todo[g0:g0 + 8]
-            n = len(grp)
-            ptrs = (C.c_void_p * n)(*[tensors[k].data_ptr() for k in grp])
-            sizes = (C.c_size_t * n)(*[tensors[k].numel() * tensors[k].element_size() for k in grp])
-            res = (C.c_uint64 * n)()
-            with torch.cuda.device(dev):
-                _check(_lib.load().mi_rast_fingerprint(n, ptrs, sizes, res, _stream_ptr(dev)))
-            for k, v in zip(grp, res):
-                t = tensors[k]
-                out[k] = (int(v), tuple(t.shape), str(t.dtype))
-                self._memo[id(t)] = (weakref.ref(t), t._version, weakref.ref(t.untyped_storage()), t.data_ptr(), out[k])
-        if len(self._memo) > 4096:   # forget tensors that are gone
-            self._memo = {i: m for i, m in self._memo.items() if m[0]() is not None}
-        return out
-
-    def lookup(self, key):
-        with self.lock:
-            e = self.entries.get(key)
-            if e is not None:
-                self.entries.move_to_end(key)
-                self.hits += 1
-            else:
-                self.misses += 1
-            return e
-
-    def insert(self, key, entry):
-        with self.lock:
-            old = self.entries.pop(key, None)
-            if old is not None:
-                self.bytes -= old["bytes"]
-            self.entries[key] = entry
-            self.bytes += entry["bytes"]
-            while self.bytes > self.max_bytes and len(self.entries) > 1:
-                _, dropped = self.entries.popitem(last=False)
-                self.bytes -= dropped["bytes"]
+    def claim(self):
+        """(prezeroed, pack_zeroed) for ONE backward: a second one through a retained graph gets (None, False) and fills for
+        itself.  pack_zeroed is also False once a hit of this cached view came in after the forward: it may have used the scratch."""
+        prezeroed, self.prezero = self.prezero, None
+        pack_zeroed, self.pack_zeroed = self.pack_zeroed, False
+        if pack_zeroed and self.epoch is not None and self.epoch[0] != self.epoch_seen:
+            pack_zeroed = False
+        return prezeroed, pack_zeroed
 
 
-_geometry_cache = None
-
-
-def enable_geometry_cache(max_bytes=64 << 30):
-    """Switches the frozen-geometry reuse on for every forward of this process (GeometryCache); returns the cache (`.stats()`).
-    Also switched on by MI_RAST_GEOMETRY_CACHE=<GiB> (or 1: 64 GiB) in the environment, for unchanged reference scripts."""
-    global _geometry_cache
-    if _geometry_cache is None:
-        _geometry_cache = GeometryCache(max_bytes)
-    else:
-        _geometry_cache.max_bytes = int(max_bytes)
-    _geometry_cache.enabled = True
-    return _geometry_cache
-
-
-def disable_geometry_cache(drop=False):
-    """Forwards recompute everything again; the cached views are kept for a later enable_geometry_cache() unless `drop`."""
-    global _geometry_cache
-    if _geometry_cache is not None:
-        _geometry_cache.enabled = False
-        if drop:
-            _geometry_cache = None
-
-
-def geometry_cache():
-    return _geometry_cache
-
-
-if os.environ.get("MI_RAST_GEOMETRY_CACHE", "") not in ("", "0"):
-    try:
-        _gib = float(os.environ["MI_RAST_GEOMETRY_CACHE"])
-    except ValueError:
-        _gib = 1.0
-    enable_geometry_cache(int((64 if _gib == 1.0 else _gib) * (1 << 30)))
+def _take_notes(geomBuffer):
+    """The autograd Functions keep a forward's notes in ctx and take them off the buffer (a cached view's buffer outlives the graph)."""
+    return geomBuffer.__dict__.pop("mi_notes", None) or ForwardNotes(0)
 
 
 # ---- features-only backward (EXTENSION, include/mi_rast.h: MI_RAST_BWD_FEATURES_ONLY) ------------------------------------------
@@ -312,9 +174,6 @@ def _features_only_applies(channels, colors_precomp, needs_input_grad, debug):
     return _features_only_backward or not any(others)
 
 
-_NOCACHE_FLAGS = _lib.MI_RAST_FULL_LISTS | _lib.MI_RAST_NO_CULL | _lib.MI_RAST_VERIFY_LISTS | _lib.MI_RAST_TILE_FWD | _lib.MI_RAST_F32_BLEND
-
-
 def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, colors, opacity, mask, scales,
                                rotations, scale_modifier, cov3D_precomp, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                                image_height, image_width, sh, degree, campos, prefiltered, debug, prezero=False):
@@ -323,12 +182,12 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
     prezero (a backward will follow: the autograd Functions set it when an input requires grad): the forward also leaves the
     backward's accumulators zero-filled -- a (P, channels) dL_dcolors tensor allocated here and the packed field gradients
     inside the geometry buffer -- stored by the blend kernel beside its own work (include/mi_rast.h: dL_dcolor_next,
-    MI_RAST_PREZERO_BWD) instead of by two fill passes in front of the backward.  The tensor is left on the returned geometry
-    buffer as `.mi_prezero` (with `.mi_pack_zeroed = True`); hand both to ONE rasterize_gaussians_backward_native call
-    (`prezeroed=`, `pack_zeroed=`).  A forward that fills a GeometryCache entry also leaves `.mi_epoch` = (the entry's epoch, its
-    value now): once a hit has bumped it, the geometry buffer's scratch is no longer known to be zero (pass pack_zeroed=False).  The dL_dcolors tensor is only made here while it is no larger than the image (P <= H W:
-    the kernel takes the fill while it at most doubles its own stores; a larger one is cheapest as the backward's own
-    torch.zeros, as before); prezero="always" makes it regardless (tests: the library then uses a fill command)."""
+    MI_RAST_PREZERO_BWD) instead of by two fill passes in front of the backward.  Both facts are left on the returned geometry
+    buffer as `.mi_notes` (ForwardNotes: `.prezero`, `.pack_zeroed`); hand what its `claim()` returns to ONE
+    rasterize_gaussians_backward_native call (`prezeroed=`, `pack_zeroed=`).  The dL_dcolors tensor is only made here while it is
+    no larger than the image (P <= H W: the kernel takes the fill while it at most doubles its own stores; a larger one is
+    cheapest as the backward's own torch.zeros, as before); prezero="always" makes it regardless (tests: the library then uses a
+    fill command)."""
     ready = _opts.features_ready          # one-shot: consumed by THIS forward whatever happens below (P == 0, an exception)
     _opts.features_ready = None
     if means3D.ndimension() != 2 or means3D.size(1) != 3:
@@ -348,10 +207,11 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
         out_mask = torch.empty((1, H, W), dtype=torch.float32, device=dev) if with_mask_depth else None
         out_depth = torch.empty((1, H, W), dtype=torch.float32, device=dev) if with_mask_depth else None
         M = sh.size(1) if sh.numel() != 0 else 0
-        t = [_contig(x) for x in (background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp,
-                                   viewmatrix, projmatrix, campos, mask)]
+        t = [contig(x) for x in (background, means3D, sh, colors, opacity, scales, rotations, cov3D_precomp,
+                                  viewmatrix, projmatrix, campos, mask)]
         bg_c, m3_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c, vm_c, pm_c, cp_c, mk_c = t
         n = C.c_int(0)
+        flags = int(_opts.flags)
         grad_colors = None
         if prezero and (P <= H * W or prezero == "always"):
             grad_colors = torch.empty((P, channels), dtype=torch.float32, device=dev)
@@ -360,77 +220,50 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
             # would be left unwritten
             raise RuntimeError("mask must hold one float32 per Gaussian on the GPU (diff_gaussian_rasterization_depth)")
         # frozen-geometry reuse (opt-in, GeometryCache): same geometry + camera as an earlier forward -> the blend stage alone
-        cache, ckey = _geometry_cache, None
-        if cache is not None and cache.enabled and not debug and not (int(_opts.flags) & _NOCACHE_FLAGS) and not prefiltered:
-            colours_from_sh = col_c is None or col_c.numel() == 0
-            # the uncached call's device / dtype checks, in its order and with its messages, before a fingerprint kernel reads data_ptr()
-            for x, name in ((bg_c, "bg"), (m3_c, "means3D"), (sh_c, "sh"), (col_c, "colors_precomp"), (op_c, "opacities"),
-                            (sc_c, "scales"), (rot_c, "rotations"), (cov_c, "cov3D_precomp"), (vm_c, "viewmatrix"),
-                            (pm_c, "projmatrix"), (cp_c, "campos")):
-                _dev_ptr(x, name, dev)
-            fps = cache.fingerprints([m3_c, op_c, sc_c, rot_c, cov_c, sh_c if colours_from_sh else None, vm_c, pm_c, cp_c], dev)
-            ckey = (dev.index, P, H, W, float(tan_fovx), float(tan_fovy), float(scale_modifier), int(degree), int(M) if colours_from_sh else -1,
-                    int(_opts.flags), tuple(fps))
+        cache, ckey = geometry_cache(), None
+        if cache is not None and cache.eligible(debug, prefiltered, flags):
+            ckey = cache.key(dev, P, H, W, tan_fovx, tan_fovy, scale_modifier, degree, M, flags, bg_c, m3_c, sh_c, col_c, op_c,
+                             sc_c, rot_c, cov_c, vm_c, pm_c, cp_c)
             hit = cache.lookup(ckey)
             if hit is not None:
                 hit["epoch"][0] += 1                 # the miss forward's pre-zeroed scratch is no longer its backward's alone
                 img_t = torch.empty(hit["img_bytes"], dtype=torch.uint8, device=dev)
                 with torch.cuda.device(dev):
                     rc = L.mi_rast_forward_reuse(
-                        P, int(channels), int(hit["num_rendered"]), _dev_ptr(bg_c, "bg", dev), W, H, _dev_ptr(col_c, "colors_precomp", dev),
+                        P, int(channels), int(hit["num_rendered"]), dev_ptr(bg_c, "bg", dev), W, H, dev_ptr(col_c, "colors_precomp", dev),
                         hit["geom"].data_ptr(), hit["blend_list"].data_ptr(), hit["ranges"].data_ptr(), hit["words"].data_ptr(),
-                        img_t.data_ptr(), int(hit["longest_run"]), _dev_ptr(mk_c, "mask", dev) if with_mask_depth else None,
+                        img_t.data_ptr(), int(hit["longest_run"]), dev_ptr(mk_c, "mask", dev) if with_mask_depth else None,
                         out_color.data_ptr(), out_mask.data_ptr() if with_mask_depth else None,
-                        out_depth.data_ptr() if with_mask_depth else None, int(_opts.flags),
+                        out_depth.data_ptr() if with_mask_depth else None, flags,
                         None if ready is None else C.c_void_p(ready.cuda_event),
-                        None if grad_colors is None else grad_colors.data_ptr(), _stream_ptr(dev))
+                        None if grad_colors is None else grad_colors.data_ptr(), stream_ptr(dev))
                 del ready
-                _check(rc)
-                geom_t = hit["geom"].view(-1)        # a new tensor object over the shared storage: the notes below are per forward
-                geom_t.mi_flags = int(_opts.flags)
-                if grad_colors is not None:
-                    geom_t.mi_prezero = grad_colors
-                    geom_t.mi_pack_zeroed = False    # (the packed-gradient scratch is shared between the forwards of a cached view: its backward fills it)
+                check(rc)
+                geom_t = hit["geom"].view(-1)        # a new tensor object over the shared storage: the notes are per forward
+                geom_t.mi_notes = ForwardNotes.for_hit(flags, grad_colors)
                 res = (hit["num_rendered"], out_color) + ((out_mask, out_depth) if with_mask_depth else ()) + \
                       (hit["radii"].clone(), geom_t, hit["blend_list"], img_t)   # (a caller may change its radii in place)
                 return res
         with torch.cuda.device(dev):
             rc = L.mi_rast_forward(
                 geom.cb, None, binning.cb, None, img.cb, None, P, int(degree), int(M), int(channels),
-                _dev_ptr(bg_c, "bg", dev), W, H, _dev_ptr(m3_c, "means3D", dev), _dev_ptr(sh_c, "sh", dev),
-                _dev_ptr(col_c, "colors_precomp", dev), _dev_ptr(op_c, "opacities", dev),
-                _dev_ptr(sc_c, "scales", dev), float(scale_modifier), _dev_ptr(rot_c, "rotations", dev),
-                _dev_ptr(cov_c, "cov3D_precomp", dev), _dev_ptr(vm_c, "viewmatrix", dev),
-                _dev_ptr(pm_c, "projmatrix", dev), _dev_ptr(cp_c, "campos", dev), float(tan_fovx), float(tan_fovy),
-                int(bool(prefiltered)), _dev_ptr(mk_c, "mask", dev) if with_mask_depth else None,
+                dev_ptr(bg_c, "bg", dev), W, H, dev_ptr(m3_c, "means3D", dev), dev_ptr(sh_c, "sh", dev),
+                dev_ptr(col_c, "colors_precomp", dev), dev_ptr(op_c, "opacities", dev),
+                dev_ptr(sc_c, "scales", dev), float(scale_modifier), dev_ptr(rot_c, "rotations", dev),
+                dev_ptr(cov_c, "cov3D_precomp", dev), dev_ptr(vm_c, "viewmatrix", dev),
+                dev_ptr(pm_c, "projmatrix", dev), dev_ptr(cp_c, "campos", dev), float(tan_fovx), float(tan_fovy),
+                int(bool(prefiltered)), dev_ptr(mk_c, "mask", dev) if with_mask_depth else None,
                 out_color.data_ptr(), out_mask.data_ptr() if with_mask_depth else None,
                 out_depth.data_ptr() if with_mask_depth else None, radii.data_ptr(), int(bool(debug)),
-                int(_opts.flags) | (_lib.MI_RAST_PREZERO_BWD if prezero else 0),
+                flags | (_lib.MI_RAST_PREZERO_BWD if prezero else 0),
                 None if ready is None else C.c_void_p(ready.cuda_event),
-                None if grad_colors is None else grad_colors.data_ptr(), _stream_ptr(dev), C.byref(n))
+                None if grad_colors is None else grad_colors.data_ptr(), stream_ptr(dev), C.byref(n))
         del ready
-        geom.tensor.mi_flags = int(_opts.flags)   # the backward re-takes the forward's decisions: it needs the same flags
-        _check(rc)
-        if prezero:
-            geom.tensor.mi_pack_zeroed = True
-            if grad_colors is not None:
-                geom.tensor.mi_prezero = grad_colors
+        check(rc)
         rendered = n.value
-        if ckey is not None:
-            # first visit of this (geometry, camera): keep what the geometry-only stages produced.  The blend list (first field of
-            # the binning buffer, include/mi_rast.h) is copied at its real length, tile ranges and the 16 words behind the R partial
-            # sums likewise; the geometry buffer is kept as it is (this forward's backward shares it).
-            _, ioff = _lib.image_layout(W, H)
-            tiles = ((W + 15) // 16) * ((H + 15) // 16)
-            words = img.tensor[ioff["num_rendered"] + 8192:ioff["num_rendered"] + 8192 + 64].clone()
-            n_list = int(words.view(torch.int32)[0].item()) if rendered > 0 else 0   # entries the lists hold (lean: <= num_rendered)
-            entry = {"geom": geom.tensor, "num_rendered": rendered, "radii": radii.clone(), "img_bytes": int(img.tensor.numel()),
-                     "blend_list": binning.tensor[:max(4 * n_list, 4)].clone(), "ranges": img.tensor[ioff["ranges"]:ioff["ranges"] + 8 * tiles].clone(),
-                     "words": words, "longest_run": int(L.mi_rast_last_longest_run()), "epoch": [0]}
-            entry["bytes"] = sum(int(entry[k].numel()) * entry[k].element_size() for k in ("geom", "blend_list", "ranges", "words", "radii"))
-            cache.insert(ckey, entry)
-            if prezero:
-                geom.tensor.mi_epoch = (entry["epoch"], 0)   # the backward takes the zeroed scratch only while no hit came in between
+        entry = None if ckey is None else cache.capture(ckey, W, H, rendered, radii, geom.tensor, binning.tensor, img.tensor)
+        # (the backward takes the zeroed scratch of a cached view only while no hit came in between: the entry's epoch)
+        geom.tensor.mi_notes = ForwardNotes(flags, grad_colors, bool(prezero), entry["epoch"] if (entry and prezero) else None)
     else:
         out_color = torch.zeros((channels, H, W), dtype=torch.float32, device=dev)
         out_mask = torch.zeros((1, H, W), dtype=torch.float32, device=dev) if with_mask_depth else None
@@ -464,8 +297,11 @@ def set_features_ready_event(event) -> None:
 
 def _flags_of(geomBuffer, flags):
     """The MI_RAST_* flags a backward must run with are those of the forward that filled `geomBuffer`: given explicitly
-    (the autograd Functions keep them in ctx), else the note the native forward left on its tensor, else none."""
-    return flags if flags is not None else getattr(geomBuffer, "mi_flags", 0)
+    (the autograd Functions keep the forward's notes in ctx), else the notes the native forward left on its tensor, else none."""
+    if flags is not None:
+        return flags
+    notes = getattr(geomBuffer, "mi_notes", None)
+    return 0 if notes is None else notes.flags
 
 
 def rasterize_gaussians_backward_native(channels, with_mask_depth, background, means3D, radii, colors, scales,
@@ -488,6 +324,9 @@ def rasterize_gaussians_backward_native(channels, with_mask_depth, background, m
     _check_widths(channels, background, colors, P)
     if dL_dout_color.ndimension() != 3 or dL_dout_color.size(0) != channels:
         raise RuntimeError(f"dL_dout_color must have dimensions ({channels}, H, W); got {tuple(dL_dout_color.shape)}")
+    if features_only and (with_mask_depth or colors.numel() == 0):
+        raise RuntimeError("features_only backward needs precomputed colours and the plain (not DEPTH) rasterizer")
+    full = not features_only
     o = dict(device=dev, dtype=torch.float32)
     # The reference allocates ten zero tensors (rasterize_points.cu:151-159).  Same tensors here: dL_dcolors and dL_dsh,
     # which the kernels accumulate into, zero-filled; the others carved from ONE uninitialised block that
@@ -495,84 +334,62 @@ def rasterize_gaussians_backward_native(channels, with_mask_depth, background, m
     # of fill traffic and nine fill launches less.  dL_dcolors -- the one gradient SAGA's feature training keeps
     # (`_point_features.grad`) -- has its own storage, so holding it does not pin the geometry gradients.
     # `debug` poisons the block with NaN first: a row the library failed to write would surface in the gradients.
-    shapes = [("dL_dmeans3D", (P, 3)), ("dL_dmeans2D", (P, 3)), ("dL_dcolors", (P, channels)), ("dL_dconic", (P, 2, 2)),
-              ("dL_dopacity", (P, 1)), ("dL_dcov3D", (P, 6)), ("dL_dsh", (P, M, 3)), ("dL_dscales", (P, 3)),
-              ("dL_drotations", (P, 4))]
-    if with_mask_depth:
-        shapes.append(("dL_dmask", (P, 1)))   # DEPTH/rasterize_points.cu:167: torch::zeros({P, 1})
-    shapes = [x for x in shapes if x[0] not in ("dL_dcolors", "dL_dsh")]
-    if features_only:
-        if with_mask_depth or colors.numel() == 0:
-            raise RuntimeError("features_only backward needs precomputed colours and the plain (not DEPTH) rasterizer")
-        if pack_zeroed is None:
-            pack_zeroed = prezeroed is not None
-        if prezeroed is not None and (tuple(prezeroed.shape) != (P, channels) or prezeroed.device != dev):
-            prezeroed = None
-        dL_dcolors = prezeroed if prezeroed is not None else torch.zeros((P, channels), **o)
-        if P != 0:
-            t = [_contig(x) for x in (background, means3D, colors, viewmatrix, projmatrix, campos, dL_dout_color, radii)]
-            bg_c, m3_c, col_c, vm_c, pm_c, cp_c, dpix_c, radii_c = t
-            with torch.cuda.device(dev):
-                rc = L.mi_rast_backward(
-                    P, int(degree), 0, int(channels), int(R), _dev_ptr(bg_c, "bg", dev), W, H,
-                    _dev_ptr(m3_c, "means3D", dev), None, _dev_ptr(col_c, "colors_precomp", dev), None, float(scale_modifier), None,
-                    None, _dev_ptr(vm_c, "viewmatrix", dev), _dev_ptr(pm_c, "projmatrix", dev), _dev_ptr(cp_c, "campos", dev),
-                    float(tan_fovx), float(tan_fovy), _dev_ptr(radii_c, "radii", dev, torch.int32), geomBuffer.data_ptr(),
-                    binningBuffer.data_ptr(), imageBuffer.data_ptr(), _dev_ptr(dpix_c, "dL_dout_color", dev), None,
-                    None, None, None, dL_dcolors.data_ptr(), None, None, None, None, None, None, 0,
-                    int(_flags_of(geomBuffer, flags)) | _lib.MI_RAST_BWD_FEATURES_ONLY | (_lib.MI_RAST_PREZERO_BWD if pack_zeroed else 0),
-                    _stream_ptr(dev))
-            _check(rc)
-        return None, dL_dcolors, None, None, None, None, None, None
-    sizes = []
-    for _n, shp in shapes:
-        n = 1
-        for d in shp:
-            n *= d
-        sizes.append((n + 3) // 4 * 4)  # keep every tensor 16-byte aligned
-    flat = torch.empty(sum(sizes), **o)
-    if debug:
-        flat.fill_(float("nan"))
+    # The features-only backward has dL_dcolors alone: no block, no dL_dsh, and the library is told M = 0 and debug = 0.
+    g = {}
+    if full:
+        shapes = [("dL_dmeans3D", (P, 3)), ("dL_dmeans2D", (P, 3)), ("dL_dconic", (P, 2, 2)), ("dL_dopacity", (P, 1)),
+                  ("dL_dcov3D", (P, 6)), ("dL_dscales", (P, 3)), ("dL_drotations", (P, 4))]
+        if with_mask_depth:
+            shapes.append(("dL_dmask", (P, 1)))   # DEPTH/rasterize_points.cu:167: torch::zeros({P, 1})
+        counts = [math.prod(shp) for _, shp in shapes]
+        starts = [0]
+        for n in counts:
+            starts.append(starts[-1] + (n + 3) // 4 * 4)   # keep every tensor 16-byte aligned
+        flat = torch.empty(starts[-1], **o)
+        if debug:
+            flat.fill_(float("nan"))
+        for (name, shp), n, off in zip(shapes, counts, starts):
+            g[name] = flat[off:off + n].view(shp)
     if pack_zeroed is None:
         pack_zeroed = prezeroed is not None
-    if prezeroed is not None and (tuple(prezeroed.shape) != (P, channels) or prezeroed.device != dev or debug):
+    if prezeroed is not None and (tuple(prezeroed.shape) != (P, channels) or prezeroed.device != dev or (debug and full)):
         prezeroed = None
-    g = {"dL_dcolors": prezeroed if prezeroed is not None else torch.zeros((P, channels), **o), "dL_dsh": torch.zeros((P, M, 3), **o)}
-    off = 0
-    for (name, shp), n in zip(shapes, sizes):
-        cnt = 1
-        for d in shp:
-            cnt *= d
-        g[name] = flat[off:off + cnt].view(shp)
-        off += n
-    dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dconic = g["dL_dmeans3D"], g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dconic"]
-    dL_dopacity, dL_dcov3D, dL_dsh, dL_dscales = g["dL_dopacity"], g["dL_dcov3D"], g["dL_dsh"], g["dL_dscales"]
-    dL_drotations = g["dL_drotations"]
-    dL_dmask = g.get("dL_dmask")
+    g["dL_dcolors"] = prezeroed if prezeroed is not None else torch.zeros((P, channels), **o)
+    if full:
+        g["dL_dsh"] = torch.zeros((P, M, 3), **o)
     if P != 0:
-        t = [_contig(x) for x in (background, means3D, sh, colors, scales, rotations, cov3D_precomp, viewmatrix,
-                                   projmatrix, campos, dL_dout_color, dL_dout_mask, radii)]
+        def only_full(x):
+            return x if full else None
+
+        def grad(name, present=True):
+            return g[name].data_ptr() if (present and name in g) else None
+
+        t = [contig(x) for x in (background, means3D, only_full(sh), colors, only_full(scales), only_full(rotations),
+                                  only_full(cov3D_precomp), viewmatrix, projmatrix, campos, dL_dout_color,
+                                  dL_dout_mask if with_mask_depth else None, radii)]
         bg_c, m3_c, sh_c, col_c, sc_c, rot_c, cov_c, vm_c, pm_c, cp_c, dpix_c, dmask_c, radii_c = t
         with torch.cuda.device(dev):
             rc = L.mi_rast_backward(
-                P, int(degree), int(M), int(channels), int(R), _dev_ptr(bg_c, "bg", dev), W, H,
-                _dev_ptr(m3_c, "means3D", dev), _dev_ptr(sh_c, "sh", dev), _dev_ptr(col_c, "colors_precomp", dev),
-                _dev_ptr(sc_c, "scales", dev), float(scale_modifier), _dev_ptr(rot_c, "rotations", dev),
-                _dev_ptr(cov_c, "cov3D_precomp", dev), _dev_ptr(vm_c, "viewmatrix", dev),
-                _dev_ptr(pm_c, "projmatrix", dev), _dev_ptr(cp_c, "campos", dev), float(tan_fovx), float(tan_fovy),
-                _dev_ptr(radii_c, "radii", dev, torch.int32), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-                imageBuffer.data_ptr(), _dev_ptr(dpix_c, "dL_dout_color", dev),
-                _dev_ptr(dmask_c, "dL_dout_mask", dev) if with_mask_depth else None,
-                dL_dmeans2D.data_ptr(), dL_dconic.data_ptr(), dL_dopacity.data_ptr(), dL_dcolors.data_ptr(),
-                dL_dmask.data_ptr() if with_mask_depth else None, dL_dmeans3D.data_ptr(), dL_dcov3D.data_ptr(),
-                dL_dsh.data_ptr() if M > 0 else None, dL_dscales.data_ptr(), dL_drotations.data_ptr(),
-                int(bool(debug)), int(_flags_of(geomBuffer, flags)) | (_lib.MI_RAST_PREZERO_BWD if pack_zeroed else 0),
-                _stream_ptr(dev))
-        _check(rc)
+                P, int(degree), int(M) if full else 0, int(channels), int(R), dev_ptr(bg_c, "bg", dev), W, H,
+                dev_ptr(m3_c, "means3D", dev), dev_ptr(sh_c, "sh", dev), dev_ptr(col_c, "colors_precomp", dev),
+                dev_ptr(sc_c, "scales", dev), float(scale_modifier), dev_ptr(rot_c, "rotations", dev),
+                dev_ptr(cov_c, "cov3D_precomp", dev), dev_ptr(vm_c, "viewmatrix", dev),
+                dev_ptr(pm_c, "projmatrix", dev), dev_ptr(cp_c, "campos", dev), float(tan_fovx), float(tan_fovy),
+                dev_ptr(radii_c, "radii", dev, torch.int32), geomBuffer.data_ptr(), binningBuffer.data_ptr(),
+                imageBuffer.data_ptr(), dev_ptr(dpix_c, "dL_dout_color", dev), dev_ptr(dmask_c, "dL_dout_mask", dev),
+                grad("dL_dmeans2D"), grad("dL_dconic"), grad("dL_dopacity"), grad("dL_dcolors"), grad("dL_dmask"),
+                grad("dL_dmeans3D"), grad("dL_dcov3D"), grad("dL_dsh", M > 0), grad("dL_dscales"), grad("dL_drotations"),
+                int(bool(debug)) if full else 0,
+                int(_flags_of(geomBuffer, flags)) | (0 if full else _lib.MI_RAST_BWD_FEATURES_ONLY)
+                | (_lib.MI_RAST_PREZERO_BWD if pack_zeroed else 0), stream_ptr(dev))
+        check(rc)
+    if features_only:
+        return None, g["dL_dcolors"], None, None, None, None, None, None
     if with_mask_depth:
-        return (dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmask, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-                dL_drotations)
-    return dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations
+        return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmask"], g["dL_dmeans3D"], g["dL_dcov3D"], g["dL_dsh"],
+                g["dL_dscales"], g["dL_drotations"])
+    return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dcov3D"], g["dL_dsh"], g["dL_dscales"],
+            g["dL_drotations"])
 
 
 def mark_visible_native(means3D, viewmatrix, projmatrix):
@@ -582,11 +399,11 @@ def mark_visible_native(means3D, viewmatrix, projmatrix):
     dev = means3D.device
     present = torch.zeros(P, dtype=torch.bool, device=dev)
     if P != 0:
-        m3_c, vm_c, pm_c = _contig(means3D), _contig(viewmatrix), _contig(projmatrix)
+        m3_c, vm_c, pm_c = contig(means3D), contig(viewmatrix), contig(projmatrix)
         with torch.cuda.device(dev):
-            rc = L.mi_rast_mark_visible(P, _dev_ptr(m3_c, "means3D", dev), _dev_ptr(vm_c, "viewmatrix", dev),
-                                        _dev_ptr(pm_c, "projmatrix", dev), present.data_ptr(), _stream_ptr(dev))
-        _check(rc)
+            rc = L.mi_rast_mark_visible(P, dev_ptr(m3_c, "means3D", dev), dev_ptr(vm_c, "viewmatrix", dev),
+                                        dev_ptr(pm_c, "projmatrix", dev), present.data_ptr(), stream_ptr(dev))
+        check(rc)
     return present
 
 
@@ -605,20 +422,20 @@ def rasterize_mask_gaussians_native(means3D, opacity, mask, scales, rotations, s
     rendered = 0
     if P != 0:
         out_mask = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-        t = [_contig(x) for x in (means3D, opacity, mask, scales, rotations, cov3D_precomp, viewmatrix, projmatrix)]
+        t = [contig(x) for x in (means3D, opacity, mask, scales, rotations, cov3D_precomp, viewmatrix, projmatrix)]
         m3_c, op_c, mk_c, sc_c, rot_c, cov_c, vm_c, pm_c = t
         n = C.c_int(0)
         with torch.cuda.device(dev):
             rc = L.mi_rast_mask_forward(
-                geom.cb, None, binning.cb, None, img.cb, None, P, W, H, _dev_ptr(m3_c, "means3D", dev),
-                _dev_ptr(op_c, "opacities", dev), _dev_ptr(mk_c, "mask", dev), _dev_ptr(sc_c, "scales", dev),
-                float(scale_modifier), _dev_ptr(rot_c, "rotations", dev), _dev_ptr(cov_c, "cov3D_precomp", dev),
-                _dev_ptr(vm_c, "viewmatrix", dev), _dev_ptr(pm_c, "projmatrix", dev), float(tan_fovx),
+                geom.cb, None, binning.cb, None, img.cb, None, P, W, H, dev_ptr(m3_c, "means3D", dev),
+                dev_ptr(op_c, "opacities", dev), dev_ptr(mk_c, "mask", dev), dev_ptr(sc_c, "scales", dev),
+                float(scale_modifier), dev_ptr(rot_c, "rotations", dev), dev_ptr(cov_c, "cov3D_precomp", dev),
+                dev_ptr(vm_c, "viewmatrix", dev), dev_ptr(pm_c, "projmatrix", dev), float(tan_fovx),
                 float(tan_fovy), int(bool(prefiltered)), out_mask.data_ptr(), radii.data_ptr(), int(bool(debug)),
-                int(_opts.flags), _stream_ptr(dev), C.byref(n))
-        _check(rc)
+                int(_opts.flags), stream_ptr(dev), C.byref(n))
+        check(rc)
         rendered = n.value
-        geom.tensor.mi_flags = int(_opts.flags)
+        geom.tensor.mi_notes = ForwardNotes(_opts.flags)
     else:
         out_mask = torch.zeros((1, H, W), dtype=torch.float32, device=dev)
     return rendered, out_mask, radii, geom.tensor, binning.tensor, img.tensor
@@ -631,13 +448,13 @@ def rasterize_mask_gaussians_backward_native(means3D, dL_dout_mask, geomBuffer, 
     dev = means3D.device
     dL_dmask = torch.zeros((P, 1), dtype=torch.float32, device=dev)   # DEPTH/rasterize_points.cu:349
     if P != 0:
-        d_c = _contig(dL_dout_mask)
+        d_c = contig(dL_dout_mask)
         with torch.cuda.device(dev):
             rc = L.mi_rast_mask_backward(P, int(R), W, H, geomBuffer.data_ptr(), binningBuffer.data_ptr(),
-                                         imageBuffer.data_ptr(), _dev_ptr(d_c, "dL_dout_mask", dev),
+                                         imageBuffer.data_ptr(), dev_ptr(d_c, "dL_dout_mask", dev),
                                          dL_dmask.data_ptr(), int(bool(debug)), int(_flags_of(geomBuffer, flags)),
-                                         _stream_ptr(dev))
-        _check(rc)
+                                         stream_ptr(dev))
+        check(rc)
     return dL_dmask
 
 
@@ -647,6 +464,49 @@ def rasterize_mask_gaussians_backward_native(means3D, dL_dout_mask, geomBuffer, 
 
 _MSG_COLORS = 'Please provide excatly one of either SHs or precomputed colors!'
 _MSG_COV = 'Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!'
+_SNAPSHOT_FW = ("snapshot_fw.dump", "\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
+_SNAPSHOT_BW = ("snapshot_bw.dump", "\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
+
+
+def _snapshot_call(debug, args, fn, path, message):
+    """fn(*args); under `debug` the reference's snapshot: a CPU copy of `args` taken first and saved when the call raises."""
+    if not debug:
+        return fn(*args)
+    cpu_args = cpu_deep_copy_tuple(args)  # Copy them before they can be corrupted
+    try:
+        return fn(*args)
+    except Exception as ex:
+        torch.save(cpu_args, path)
+        print(message)
+        raise ex
+
+
+def _one_of_colors(shs, colors_precomp):
+    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        raise Exception(_MSG_COLORS)
+
+
+def _one_of_cov(scales, rotations, cov3D_precomp):
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception(_MSG_COV)
+
+
+def _or_empty(*tensors):
+    """The reference's default for an argument that was not given: an empty CPU tensor (-> NULL in the library call)."""
+    return tuple(torch.Tensor([]) if t is None else t for t in tensors)
+
+
+class _RasterizerModule(nn.Module):
+    def __init__(self, raster_settings):
+        super().__init__()
+        self.raster_settings = raster_settings
+
+    def markVisible(self, positions):
+        with torch.no_grad():
+            rs = self.raster_settings
+            visible = mark_visible_native(positions, rs.viewmatrix, rs.projmatrix)
+        return visible
 
 
 def _make_plain(channels):
@@ -665,28 +525,13 @@ def _make_plain(channels):
             # (needs_input_grad is requires_grad of the inputs whatever the grad mode: render.py's no_grad forwards of a model whose
             # parameters require grad would zero 128 MB per view for a backward that never comes)
             prezero = _opts.grad_mode and bool(any(ctx.needs_input_grad)) and not rs.debug
-
-            def call():
-                (bg, m3, col, op, sc, rot, smod, cov, vm, pm, tx, ty, ih, iw, sh_, deg, cp, pre, dbg) = args
-                return rasterize_gaussians_native(channels, False, bg, m3, col, op, None, sc, rot, smod, cov, vm, pm,
-                                                  tx, ty, ih, iw, sh_, deg, cp, pre, dbg, prezero=prezero)
-
-            if rs.debug:
-                cpu_args = cpu_deep_copy_tuple(args)  # Copy them before they can be corrupted
-                try:
-                    num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = call()
-                except Exception as ex:
-                    torch.save(cpu_args, "snapshot_fw.dump")
-                    print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                    raise ex
-            else:
-                num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = call()
+            # (the native forward is looked up in this module when the call is made: tests replace it)
+            num_rendered, color, radii, geomBuffer, binningBuffer, imgBuffer = _snapshot_call(
+                rs.debug, args, lambda bg, m3, col, op, *rest: rasterize_gaussians_native(
+                    channels, False, bg, m3, col, op, None, *rest, prezero=prezero), *_SNAPSHOT_FW)
             ctx.raster_settings = rs
             ctx.num_rendered = num_rendered
-            ctx.mi_flags = getattr(geomBuffer, "mi_flags", 0)
-            ctx.mi_prezero = geomBuffer.__dict__.pop("mi_prezero", None)   # one-shot: the first backward takes them
-            ctx.mi_pack_zeroed = bool(geomBuffer.__dict__.pop("mi_pack_zeroed", False))
-            ctx.mi_epoch = geomBuffer.__dict__.pop("mi_epoch", None)   # (cache entry epoch, value): a cacheable miss (GeometryCache)
+            ctx.mi_notes = _take_notes(geomBuffer)   # flags + who may skip the fills: the first backward claims them
             ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
                                   binningBuffer, imgBuffer)
             ctx.mark_non_differentiable(radii)
@@ -706,33 +551,13 @@ def _make_plain(channels):
             args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                     rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, sh, rs.sh_degree, rs.campos,
                     geomBuffer, num_rendered, binningBuffer, imgBuffer, rs.debug)
-
-            prezeroed, ctx.mi_prezero = ctx.mi_prezero, None   # (a second backward through a retained graph fills for itself)
-            pack_zeroed, ctx.mi_pack_zeroed = ctx.mi_pack_zeroed, False
-            if pack_zeroed and ctx.mi_epoch is not None and ctx.mi_epoch[0][0] != ctx.mi_epoch[1]:
-                pack_zeroed = False   # a hit of this cached view shares the scratch and may have used it: fill it again
-
+            prezeroed, pack_zeroed = ctx.mi_notes.claim()
             feat_only = _features_only_applies(channels, colors_precomp, ctx.needs_input_grad, rs.debug)
-
-            def call():
-                (bg, m3, rad, col, sc, rot, smod, cov, vm, pm, tx, ty, gout, sh_, deg, cp, gb, nr, bb, ib, dbg) = args
-                return rasterize_gaussians_backward_native(channels, False, bg, m3, rad, col, sc, rot, smod, cov, vm,
-                                                           pm, tx, ty, gout, None, sh_, deg, cp, gb, nr, bb, ib, dbg,
-                                                           flags=ctx.mi_flags, prezeroed=prezeroed, pack_zeroed=pack_zeroed,
-                                                           features_only=feat_only)
-
-            if rs.debug:
-                cpu_args = cpu_deep_copy_tuple(args)
-                try:
-                    res = call()
-                except Exception as ex:
-                    torch.save(cpu_args, "snapshot_bw.dump")
-                    print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                    raise ex
-            else:
-                res = call()
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = res
+             grad_scales, grad_rotations) = _snapshot_call(
+                rs.debug, args, lambda *a: rasterize_gaussians_backward_native(
+                    channels, False, *a[:13], None, *a[13:], flags=ctx.mi_notes.flags, prezeroed=prezeroed,
+                    pack_zeroed=pack_zeroed, features_only=feat_only), *_SNAPSHOT_BW)
             return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_opacities, grad_scales,
                     grad_rotations, grad_cov3Ds_precomp, None)
 
@@ -748,37 +573,14 @@ def _make_plain(channels):
         finally:
             _opts.grad_mode = True
 
-    class GaussianRasterizer(nn.Module):
-        def __init__(self, raster_settings):
-            super().__init__()
-            self.raster_settings = raster_settings
-
-        def markVisible(self, positions):
-            with torch.no_grad():
-                rs = self.raster_settings
-                visible = mark_visible_native(positions, rs.viewmatrix, rs.projmatrix)
-            return visible
-
+    class GaussianRasterizer(_RasterizerModule):
         def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
                     cov3D_precomp=None):
-            raster_settings = self.raster_settings
-            if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-                raise Exception(_MSG_COLORS)
-            if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                    ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-                raise Exception(_MSG_COV)
-            if shs is None:
-                shs = torch.Tensor([])
-            if colors_precomp is None:
-                colors_precomp = torch.Tensor([])
-            if scales is None:
-                scales = torch.Tensor([])
-            if rotations is None:
-                rotations = torch.Tensor([])
-            if cov3D_precomp is None:
-                cov3D_precomp = torch.Tensor([])
+            _one_of_colors(shs, colors_precomp)
+            _one_of_cov(scales, rotations, cov3D_precomp)
+            shs, colors_precomp, scales, rotations, cov3D_precomp = _or_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                       cov3D_precomp, raster_settings)
+                                       cov3D_precomp, self.raster_settings)
 
     return _RasterizeGaussians, rasterize_gaussians, GaussianRasterizer
 
@@ -795,27 +597,13 @@ def _make_depth():
             args = (rs.bg, means3D, colors_precomp, opacities, mask, scales, rotations, rs.scale_modifier,
                     cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height,
                     rs.image_width, sh, rs.sh_degree, rs.campos, rs.prefiltered, rs.debug)
-
-            def call():
-                (bg, m3, col, op, mk, sc, rot, smod, cov, vm, pm, tx, ty, ih, iw, sh_, deg, cp, pre, dbg) = args
-                return rasterize_gaussians_native(channels, True, bg, m3, col, op, mk, sc, rot, smod, cov, vm, pm, tx,
-                                                  ty, ih, iw, sh_, deg, cp, pre, dbg)
-
-            if rs.debug:
-                cpu_args = cpu_deep_copy_tuple(args)
-                try:
-                    res = call()
-                except Exception as ex:
-                    torch.save(cpu_args, "snapshot_fw.dump")
-                    print("\nAn error occured in forward. Please forward snapshot_fw.dump for debugging.")
-                    raise ex
-            else:
-                res = call()
-            num_rendered, color, out_mask, depth, radii, geomBuffer, binningBuffer, imgBuffer = res
+            # (never asks for prezero: its backward fills for itself)
+            num_rendered, color, out_mask, depth, radii, geomBuffer, binningBuffer, imgBuffer = _snapshot_call(
+                rs.debug, args, lambda *a: rasterize_gaussians_native(channels, True, *a), *_SNAPSHOT_FW)
             ctx.mask_shape = mask.shape
             ctx.raster_settings = rs
             ctx.num_rendered = num_rendered
-            ctx.mi_flags = getattr(geomBuffer, "mi_flags", 0)
+            ctx.mi_notes = _take_notes(geomBuffer)
             ctx.save_for_backward(colors_precomp, means3D, scales, rotations, cov3Ds_precomp, radii, sh, geomBuffer,
                                   binningBuffer, imgBuffer)
             ctx.mark_non_differentiable(radii)
@@ -837,26 +625,10 @@ def _make_depth():
             args = (rs.bg, means3D, radii, colors_precomp, scales, rotations, rs.scale_modifier, cov3Ds_precomp,
                     rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, grad_out_color, grad_out_mask, sh,
                     rs.sh_degree, rs.campos, geomBuffer, num_rendered, binningBuffer, imgBuffer, rs.debug)
-
-            def call():
-                (bg, m3, rad, col, sc, rot, smod, cov, vm, pm, tx, ty, gout, gmask, sh_, deg, cp, gb, nr, bb, ib,
-                 dbg) = args
-                return rasterize_gaussians_backward_native(channels, True, bg, m3, rad, col, sc, rot, smod, cov, vm,
-                                                           pm, tx, ty, gout, gmask, sh_, deg, cp, gb, nr, bb, ib, dbg,
-                                                           flags=ctx.mi_flags)
-
-            if rs.debug:
-                cpu_args = cpu_deep_copy_tuple(args)
-                try:
-                    res = call()
-                except Exception as ex:
-                    torch.save(cpu_args, "snapshot_bw.dump")
-                    print("\nAn error occured in backward. Writing snapshot_bw.dump for debugging.\n")
-                    raise ex
-            else:
-                res = call()
             (grad_means2D, grad_colors_precomp, grad_opacities, grad_mask, grad_means3D, grad_cov3Ds_precomp, grad_sh,
-             grad_scales, grad_rotations) = res
+             grad_scales, grad_rotations) = _snapshot_call(
+                rs.debug, args, lambda *a: rasterize_gaussians_backward_native(channels, True, *a, flags=ctx.mi_notes.flags),
+                *_SNAPSHOT_BW)
             # the reference hands back (P,1) (DEPTH/rasterize_points.cu:167), which autograd accepts only for a (P,1)
             # mask; same P values here, shaped like the mask that came in, so that (P,) works as well
             grad_mask = grad_mask.view(ctx.mask_shape)
@@ -874,7 +646,7 @@ def _make_depth():
             ctx.raster_settings = rs
             ctx.num_rendered = num_rendered
             ctx.mask_shape = mask.shape
-            ctx.mi_flags = getattr(geomBuffer, "mi_flags", 0)
+            ctx.mi_notes = _take_notes(geomBuffer)
             ctx.save_for_backward(means3D, means2D, opacities, scales, rotations, cov3Ds_precomp, radii, geomBuffer,
                                   binningBuffer, imgBuffer)
             ctx.mark_non_differentiable(radii)
@@ -891,7 +663,7 @@ def _make_depth():
              imgBuffer) = ctx.saved_tensors
             grad_mask = rasterize_mask_gaussians_backward_native(means3D, grad_out_mask, geomBuffer, ctx.num_rendered,
                                                                  binningBuffer, imgBuffer, rs.debug,
-                                                                 flags=ctx.mi_flags).view(ctx.mask_shape)
+                                                                 flags=ctx.mi_notes.flags).view(ctx.mask_shape)
             # only the mask receives a real gradient; the reference hands ZEROS (not None) to every other input
             # (DEPTH/.../__init__.py:278-290) -- kept, but shaped like the inputs so autograd accepts them.
             z = [torch.zeros_like(t) if need else None for t, need in
@@ -910,51 +682,20 @@ def _make_depth():
         return _RasterizeMaskGaussians.apply(means3D, means2D, opacities, mask, scales, rotations, cov3Ds_precomp,
                                              raster_settings)
 
-    class GaussianRasterizer(nn.Module):
-        def __init__(self, raster_settings):
-            super().__init__()
-            self.raster_settings = raster_settings
-
-        def markVisible(self, positions):
-            with torch.no_grad():
-                rs = self.raster_settings
-                visible = mark_visible_native(positions, rs.viewmatrix, rs.projmatrix)
-            return visible
-
+    class GaussianRasterizer(_RasterizerModule):
         def forward(self, means3D, means2D, opacities, mask, shs=None, colors_precomp=None, scales=None,
                     rotations=None, cov3D_precomp=None):
-            raster_settings = self.raster_settings
-            if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-                raise Exception(_MSG_COLORS)
-            if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                    ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-                raise Exception(_MSG_COV)
-            if shs is None:
-                shs = torch.Tensor([])
-            if colors_precomp is None:
-                colors_precomp = torch.Tensor([])
-            if scales is None:
-                scales = torch.Tensor([])
-            if rotations is None:
-                rotations = torch.Tensor([])
-            if cov3D_precomp is None:
-                cov3D_precomp = torch.Tensor([])
+            _one_of_colors(shs, colors_precomp)
+            _one_of_cov(scales, rotations, cov3D_precomp)
+            shs, colors_precomp, scales, rotations, cov3D_precomp = _or_empty(shs, colors_precomp, scales, rotations, cov3D_precomp)
             return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, mask, scales, rotations,
-                                       cov3D_precomp, raster_settings)
+                                       cov3D_precomp, self.raster_settings)
 
         def forward_mask(self, means3D, means2D, opacities, mask, scales=None, rotations=None, cov3D_precomp=None):
-            raster_settings = self.raster_settings
-            if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                    ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-                raise Exception(_MSG_COV)
-            if scales is None:
-                scales = torch.Tensor([])
-            if rotations is None:
-                rotations = torch.Tensor([])
-            if cov3D_precomp is None:
-                cov3D_precomp = torch.Tensor([])
+            _one_of_cov(scales, rotations, cov3D_precomp)
+            scales, rotations, cov3D_precomp = _or_empty(scales, rotations, cov3D_precomp)
             return rasterize_mask_gaussians(means3D, means2D, opacities, mask, scales, rotations, cov3D_precomp,
-                                            raster_settings)
+                                            self.raster_settings)
 
     return _RasterizeGaussians, _RasterizeMaskGaussians, rasterize_gaussians, rasterize_mask_gaussians, \
         GaussianRasterizer
@@ -982,16 +723,7 @@ def make_auto_rasterizer(default_channels: int = 32):
         return make_rasterizer(_channels(colors_precomp, raster_settings))[1](means3D, means2D, sh, colors_precomp, opacities, scales,
                                                                              rotations, cov3Ds_precomp, raster_settings)
 
-    class GaussianRasterizer(nn.Module):
-        def __init__(self, raster_settings):
-            super().__init__()
-            self.raster_settings = raster_settings
-
-        def markVisible(self, positions):
-            with torch.no_grad():
-                rs = self.raster_settings
-                return mark_visible_native(positions, rs.viewmatrix, rs.projmatrix)
-
+    class GaussianRasterizer(_RasterizerModule):
         def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None):
             impl = make_rasterizer(_channels(colors_precomp, self.raster_settings))[2](self.raster_settings)
             return impl(means3D=means3D, means2D=means2D, opacities=opacities, shs=shs, colors_precomp=colors_precomp, scales=scales,

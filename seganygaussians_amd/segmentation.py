@@ -22,7 +22,7 @@ from __future__ import annotations
 
 import torch
 
-from .contrastive_loss import _check, _stream
+from ._ffi import check, ptr, stream_ptr
 
 MAX_CHANNELS = 256
 MAX_QUERIES = 16
@@ -80,10 +80,6 @@ def _prepare(who: str, features, queries, gates, pre, max_q: int, qname: str):
     return features, queries, gates, layout, N, C, Q, shape
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def similarity_scores(features: torch.Tensor, queries: torch.Tensor, gates: torch.Tensor = None, pre: str = "none",
                       post: bool = True) -> torch.Tensor:
     """s_k of every row for 1 <= Q <= 16 queries: (Q, H, W) for a (C, H, W) image, (Q, P) for (P, C) points.
@@ -98,8 +94,8 @@ def similarity_scores(features: torch.Tensor, queries: torch.Tensor, gates: torc
     dev = features.device
     out = torch.empty((Q,) + shape, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _check(L.mi_segment_scores(layout, N, C, Q, features.data_ptr(), queries.data_ptr(), _ptr(gates), PRE_MODES[pre],
-                                   1 if post else 0, out.data_ptr(), _stream(dev)))
+        check(L.mi_segment_scores(layout, N, C, Q, features.data_ptr(), queries.data_ptr(), ptr(gates), PRE_MODES[pre],
+                                  1 if post else 0, out.data_ptr(), stream_ptr(dev)))
     return out
 
 
@@ -122,8 +118,8 @@ def select_by_similarity(features: torch.Tensor, queries: torch.Tensor, threshol
     mask = torch.empty(shape, device=dev, dtype=torch.bool)
     score = torch.empty(shape, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _check(L.mi_segment_select(layout, N, C, Q, features.data_ptr(), queries.data_ptr(), _ptr(gates), PRE_MODES[pre],
-                                   1 if half_shift else 0, threshold, mask.data_ptr(), score.data_ptr(), _stream(dev)))
+        check(L.mi_segment_select(layout, N, C, Q, features.data_ptr(), queries.data_ptr(), ptr(gates), PRE_MODES[pre],
+                                  1 if half_shift else 0, threshold, mask.data_ptr(), score.data_ptr(), stream_ptr(dev)))
     return mask, score
 
 
@@ -139,6 +135,6 @@ def assign_clusters(features: torch.Tensor, centers: torch.Tensor, gates: torch.
     labels = torch.empty(shape, device=dev, dtype=torch.int32)
     best = torch.empty(shape, device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _check(L.mi_segment_assign(layout, N, C, K, features.data_ptr(), centers.data_ptr(), _ptr(gates), PRE_MODES[pre],
-                                   labels.data_ptr(), best.data_ptr(), _stream(dev)))
+        check(L.mi_segment_assign(layout, N, C, K, features.data_ptr(), centers.data_ptr(), ptr(gates), PRE_MODES[pre],
+                                  labels.data_ptr(), best.data_ptr(), stream_ptr(dev)))
     return labels, best

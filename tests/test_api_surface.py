@@ -114,3 +114,50 @@ def test_channel_width_mismatches_are_refused():
         R.rasterize_gaussians_native(*args(64, torch.zeros(32), torch.zeros(2, 64)))
     with pytest.raises(RuntimeError, match=r"colors_precomp must have dimensions \(num_points, 32\)"):
         R.rasterize_gaussians_native(*args(32, torch.zeros(32), torch.zeros(2, 64)))
+
+
+def test_dev_ptr_refuses_what_the_library_cannot_read():
+    """_ffi.dev_ptr: a caller's tensor reaches the library as a pointer only when it is a GPU tensor of the expected dtype on
+    the expected device; None and an empty tensor are the reference's NULL."""
+    from seganygaussians_amd import _ffi
+    assert _ffi.dev_ptr(None, "x") is None and _ffi.dev_ptr(torch.Tensor([]), "x") is None
+    assert _ffi.ptr(None) is None and _ffi.ptr(torch.Tensor([])) is None
+    with pytest.raises(RuntimeError, match=r"x must be a GPU tensor \(got cpu\); the MI355X rasterizer has no CPU path"):
+        _ffi.dev_ptr(torch.zeros(2), "x")
+
+    class OnGpu:
+        """What dev_ptr reads of a tensor, without a GPU."""
+        is_cuda = True
+
+        def __init__(self, dtype, device):
+            self.dtype, self.device = dtype, torch.device(device)
+
+        def numel(self):
+            return 2
+
+        def data_ptr(self):
+            return 4096
+
+    with pytest.raises(RuntimeError, match=r"x must be torch.float32 \(got torch.int32\)"):
+        _ffi.dev_ptr(OnGpu(torch.int32, "cuda:0"), "x")
+    with pytest.raises(RuntimeError, match=r"x is on cuda:1, expected cuda:0"):
+        _ffi.dev_ptr(OnGpu(torch.float32, "cuda:1"), "x", torch.device("cuda:0"))
+    assert _ffi.dev_ptr(OnGpu(torch.float32, "cuda:0"), "x", torch.device("cuda:0")) == 4096
+    assert _ffi.dev_ptr(OnGpu(torch.int32, "cuda:0"), "x", None, torch.int32) == 4096
+
+
+def test_one_set_of_call_helpers():
+    """The modules that call into the library use _ffi's helpers and define none of their own."""
+    import importlib
+    import types
+    from seganygaussians_amd import _ffi
+    shared = {name: fn for name, fn in vars(_ffi).items() if isinstance(fn, types.FunctionType)}
+    assert set(shared) == {"check", "ptr", "dev_ptr", "contig", "stream_ptr"}
+    for name in ("knn", "contrastive_loss", "contrastive_frontend", "segmentation", "photometric", "mask_scales", "knn_smooth",
+                 "rasterizer", "geometry_cache"):
+        mod = importlib.import_module("seganygaussians_amd." + name)
+        for attr, value in vars(mod).items():
+            assert attr not in ("_check", "_ptr", "_stream", "_stream_ptr", "_dev_ptr", "_contig"), f"{name}.{attr}"
+            if attr in shared:
+                assert value is shared[attr], f"{name}.{attr} is a copy"
+        assert any(vars(mod).get(k) is fn for k, fn in shared.items()), f"{name} does not use _ffi"

@@ -1,4 +1,4 @@
-"""Frozen-geometry reuse (seganygaussians_amd/rasterizer.py: GeometryCache; include/mi_rast.h: mi_rast_forward_reuse,
+"""Frozen-geometry reuse (seganygaussians_amd/geometry_cache.py: GeometryCache; include/mi_rast.h: mi_rast_forward_reuse,
 mi_rast_fingerprint): a forward of the same geometry from the same camera runs the blend stage alone over what the first visit
 left.  The opt-in must change nothing: images, radii and every gradient bit for bit those of an uncached run (the atomic sums of
 the backward: up to their order), whatever tensors carry the geometry -- the same objects again (bench.py), or activation outputs

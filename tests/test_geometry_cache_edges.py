@@ -1,4 +1,4 @@
-"""Frozen-geometry reuse at its edges (seganygaussians_amd/rasterizer.py: GeometryCache; include/mi_rast.h: mi_rast_forward_reuse,
+"""Frozen-geometry reuse at its edges (seganygaussians_amd/geometry_cache.py: GeometryCache; include/mi_rast.h: mi_rast_forward_reuse,
 mi_rast_fingerprint).  tests/test_geometry_cache.py checks one render per backward, one step after the other; here the renders of
 cached views interleave -- a miss and its hits in one loss, backwards in either order, no-grad renders between a forward and its
 backward, retained graphs, gradient accumulation -- at several widths, in the three packages, with P below and above H W.
