@@ -13,26 +13,37 @@ __version__ = "0.1.0"
 DROPIN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin")
 
 
-def install_dropin(fuse_smoothing: bool = False) -> str:
+def install_dropin(fuse_smoothing: bool = False, fuse_training_step: bool = False) -> str:
     """Puts the drop-in packages (same import names as the reference's pip-installed submodules,
     environment.yml:18-21) at the FRONT of sys.path.
 
     fuse_smoothing=True (opt-in) additionally rebinds `FeatureGaussianModel.get_smoothed_point_features`
     (scene/gaussian_model_ff.py:338-364) to the fused HIP gather kernels (knn_smooth.py, include/mi_knn_smooth.h): at once
     if `scene.gaussian_model_ff` is already imported, otherwise right after it is imported.  Same signature, same column
-    draw from the CPU generator, same values and gradients; the reference's own PyTorch expression is no longer executed."""
+    draw from the CPU generator, same values and gradients; the reference's own PyTorch expression is no longer executed.
+
+    fuse_training_step=True (opt-in) patches `scene.gaussian_model.GaussianModel` in the same manner (training_step.py, DESIGN.md
+    section 18): `training_setup` swaps the optimizer it built for a FusedAdam over the same groups, and
+    `add_densification_stats` and `densify_and_prune` run the HIP kernels.  The originals stay reachable as `_reference_*`."""
     if DROPIN_DIR not in sys.path:
         sys.path.insert(0, DROPIN_DIR)
     if fuse_smoothing:
-        mod = sys.modules.get(_FF_MODULE)
-        if mod is not None and hasattr(mod, "FeatureGaussianModel"):
-            patch_feature_model(mod.FeatureGaussianModel)
-        elif not any(isinstance(f, _PatchOnImport) for f in sys.meta_path):
-            sys.meta_path.insert(0, _PatchOnImport())
+        _patch_now_or_on_import(_FF_MODULE, "FeatureGaussianModel", patch_feature_model)
+    if fuse_training_step:
+        _patch_now_or_on_import(_GM_MODULE, "GaussianModel", patch_gaussian_model)
     return DROPIN_DIR
 
 
 _FF_MODULE = "scene.gaussian_model_ff"
+_GM_MODULE = "scene.gaussian_model"
+
+
+def _patch_now_or_on_import(module_name: str, class_name: str, patch) -> None:
+    mod = sys.modules.get(module_name)
+    if mod is not None and hasattr(mod, class_name):
+        patch(getattr(mod, class_name))
+    elif not any(isinstance(f, _PatchOnImport) and f.module_name == module_name for f in sys.meta_path):
+        sys.meta_path.insert(0, _PatchOnImport(module_name, class_name, patch))
 
 
 def patch_feature_model(cls) -> None:
@@ -46,12 +57,28 @@ def patch_feature_model(cls) -> None:
     cls._mi_fused_smoothing = True
 
 
+def patch_gaussian_model(cls) -> None:
+    """Rebinds training_setup, add_densification_stats and densify_and_prune of cls (the reference's GaussianModel) to the fused
+    training step; idempotent.  The originals stay reachable as cls._reference_<name>."""
+    if getattr(cls, "_mi_fused_training_step", False):
+        return
+    from . import training_step as ts
+    for name, fn in (("training_setup", ts.fused_training_setup), ("add_densification_stats", ts.fused_add_densification_stats),
+                     ("densify_and_prune", ts.fused_densify_and_prune)):
+        setattr(cls, "_reference_" + name, getattr(cls, name))
+        setattr(cls, name, fn)
+    cls._mi_fused_training_step = True
+
+
 class _PatchOnImport:
-    """sys.meta_path finder: lets the normal machinery find scene.gaussian_model_ff, then patches the class once the
+    """sys.meta_path finder: lets the normal machinery find `module_name`, then calls patch(module.<class_name>) once the
     module has been executed."""
 
+    def __init__(self, module_name: str = _FF_MODULE, class_name: str = "FeatureGaussianModel", patch=patch_feature_model):
+        self.module_name, self.class_name, self.patch = module_name, class_name, patch
+
     def find_spec(self, name, path=None, target=None):
-        if name != _FF_MODULE:
+        if name != self.module_name:
             return None
         import importlib.util
         sys.meta_path.remove(self)
@@ -65,8 +92,8 @@ class _PatchOnImport:
 
         def exec_module(module, _inner=inner):
             _inner(module)
-            if hasattr(module, "FeatureGaussianModel"):
-                patch_feature_model(module.FeatureGaussianModel)
+            if hasattr(module, self.class_name):
+                self.patch(getattr(module, self.class_name))
             if self in sys.meta_path:
                 sys.meta_path.remove(self)
 

@@ -36,7 +36,13 @@ SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign"
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
 PHOTOMETRIC_EXPORTS = ["mi_photo_loss_workspace_bytes", "mi_photo_loss_window", "mi_photo_loss_forward", "mi_photo_loss_backward"]   # include/mi_photometric.h
 MI_PHOTO_L1, MI_PHOTO_SSIM = 1, 2
-ALL_EXPORTS = EXPORTS + MASK_SCALES_EXPORTS + SEGMENT_EXPORTS + PHOTOMETRIC_EXPORTS   # every function the headers in include/ declare
+# include/mi_rast.h, its training-step section (csrc/mi_train_step.hip)
+TRAIN_STEP_EXPORTS = ["mi_train_adam_step", "mi_train_densify_stats", "mi_train_densify_workspace_bytes", "mi_train_densify_plan",
+                      "mi_train_densify_counts", "mi_train_densify_apply"]
+MI_TRAIN_COUNTS = ["clones", "splits", "kept_originals", "kept_clones", "kept_children"]
+MI_TRAIN_COPY, MI_TRAIN_MOMENT, MI_TRAIN_XYZ, MI_TRAIN_SCALING, MI_TRAIN_ROTATION = 0, 1, 2, 3, 4
+MI_TRAIN_ADAM_MAX_TENSORS, MI_TRAIN_DENSIFY_MAX_TENSORS = 16, 32
+ALL_EXPORTS = EXPORTS + MASK_SCALES_EXPORTS + SEGMENT_EXPORTS + PHOTOMETRIC_EXPORTS + TRAIN_STEP_EXPORTS   # every function the headers in include/ declare
 MI_SEGMENT_PRE = {"none": 0, "l2": 1, "eps": 2}
 
 _lib = None
@@ -151,6 +157,19 @@ def load():
     L.mi_photo_loss_forward.argtypes = [i, i, i, i, vp, vp, C.c_double, i, vp, vp, C.c_size_t, vp, vp]
     L.mi_photo_loss_backward.restype = i
     L.mi_photo_loss_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, i, f, f, vp, vp]
+    pp, d = C.POINTER(C.c_void_p), C.c_double
+    L.mi_train_adam_step.restype = i
+    L.mi_train_adam_step.argtypes = [i, pp, pp, pp, pp, C.POINTER(C.c_size_t), C.POINTER(d), d, d, d, d, vp]
+    L.mi_train_densify_stats.restype = i
+    L.mi_train_densify_stats.argtypes = [i, vp, vp, vp, vp, vp, vp]
+    L.mi_train_densify_workspace_bytes.restype = C.c_size_t
+    L.mi_train_densify_workspace_bytes.argtypes = [i]
+    L.mi_train_densify_plan.restype = i
+    L.mi_train_densify_plan.argtypes = [i, vp, vp, vp, vp, d, d, d, d, i, vp, C.c_size_t, vp, vp]
+    L.mi_train_densify_counts.restype = i
+    L.mi_train_densify_counts.argtypes = [i, vp, C.c_size_t, C.POINTER(i), vp]
+    L.mi_train_densify_apply.restype = i
+    L.mi_train_densify_apply.argtypes = [i, C.POINTER(i), i, pp, pp, C.POINTER(i), C.POINTER(i), vp, vp, C.c_size_t, vp]
     _lib = L
     return L
 
