@@ -11,9 +11,10 @@ import sys
 __version__ = "0.1.0"
 
 DROPIN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin")
+CLUSTERING_DROPIN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dropin_clustering")
 
 
-def install_dropin(fuse_smoothing: bool = False, fuse_training_step: bool = False) -> str:
+def install_dropin(fuse_smoothing: bool = False, fuse_training_step: bool = False, fuse_clustering: bool = False) -> str:
     """Puts the drop-in packages (same import names as the reference's pip-installed submodules,
     environment.yml:18-21) at the FRONT of sys.path.
 
@@ -24,13 +25,19 @@ def install_dropin(fuse_smoothing: bool = False, fuse_training_step: bool = Fals
 
     fuse_training_step=True (opt-in) patches `scene.gaussian_model.GaussianModel` in the same manner (training_step.py, DESIGN.md
     section 18): `training_setup` swaps the optimizer it built for a FusedAdam over the same groups, and
-    `add_densification_stats` and `densify_and_prune` run the HIP kernels.  The originals stay reachable as `_reference_*`."""
+    `add_densification_stats` and `densify_and_prune` run the HIP kernels.  The originals stay reachable as `_reference_*`.
+
+    fuse_clustering=True (opt-in) additionally puts a second directory at the front of sys.path, whose only package is `hdbscan`
+    (clustering.py): `from hdbscan import HDBSCAN` then resolves to the HIP implementation, euclidean only.
+    It is a directory of its own so that a plain install_dropin() never shadows an installed `hdbscan`."""
     if DROPIN_DIR not in sys.path:
         sys.path.insert(0, DROPIN_DIR)
     if fuse_smoothing:
         _patch_now_or_on_import(_FF_MODULE, "FeatureGaussianModel", patch_feature_model)
     if fuse_training_step:
         _patch_now_or_on_import(_GM_MODULE, "GaussianModel", patch_gaussian_model)
+    if fuse_clustering and CLUSTERING_DROPIN_DIR not in sys.path:
+        sys.path.insert(0, CLUSTERING_DROPIN_DIR)
     return DROPIN_DIR
 
 

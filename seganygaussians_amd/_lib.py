@@ -20,6 +20,8 @@ MI_RAST_EQUAL_RUNS = 256   # A/B aid: XCD runs of equal tile counts in both blen
 MI_RAST_BWD_FEATURES_ONLY = 512   # mi_rast_backward: dL_dcolor alone (extension, include/mi_rast.h)
 MI_STAGES = ["preprocess", "tile_scan", "emit", "tile_sort", "blend_fwd", "blend_bwd", "geom_bwd"]
 
+# include/mi_segment.h, its clustering section (csrc/mi_cluster.hip); listed on its own and as the tail of EXPORTS
+CLUSTER_EXPORTS = ["mi_cluster_workspace_bytes", "mi_cluster_core_distances", "mi_cluster_mst", "mi_cluster_mst_rounds", "mi_cluster_labels_host"]
 EXPORTS = [
     "mi_rast_forward", "mi_rast_forward_reuse", "mi_rast_last_longest_run", "mi_rast_fingerprint", "mi_rast_features_only_supported", "mi_rast_backward", "mi_rast_mark_visible", "mi_rast_mask_forward",
     "mi_rast_mask_backward", "mi_rast_last_error", "mi_rast_version", "mi_rast_supported_channels",
@@ -30,7 +32,7 @@ EXPORTS = [
     "mi_contrastive_forward", "mi_contrastive_backward",  # include/mi_contrastive.h
     "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
     "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
-]
+] + CLUSTER_EXPORTS
 MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_scales"]   # include/mi_mask_scales.h
 SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
@@ -42,6 +44,8 @@ TRAIN_STEP_EXPORTS = ["mi_train_adam_step", "mi_train_densify_stats", "mi_train_
 MI_TRAIN_COUNTS = ["clones", "splits", "kept_originals", "kept_clones", "kept_children"]
 MI_TRAIN_COPY, MI_TRAIN_MOMENT, MI_TRAIN_XYZ, MI_TRAIN_SCALING, MI_TRAIN_ROTATION = 0, 1, 2, 3, 4
 MI_TRAIN_ADAM_MAX_TENSORS, MI_TRAIN_DENSIFY_MAX_TENSORS = 16, 32
+MI_CLUSTER_METRIC = {"euclidean": 0, "jaccard": 1}
+MI_CLUSTER_MAX_POINTS, MI_CLUSTER_MAX_CHANNELS, MI_CLUSTER_MAX_WORDS, MI_CLUSTER_MAX_CORE_K = 1 << 20, 256, 1024, 64
 ALL_EXPORTS = EXPORTS + MASK_SCALES_EXPORTS + SEGMENT_EXPORTS + PHOTOMETRIC_EXPORTS + TRAIN_STEP_EXPORTS   # every function the headers in include/ declare
 MI_SEGMENT_PRE = {"none": 0, "l2": 1, "eps": 2}
 
@@ -170,6 +174,16 @@ def load():
     L.mi_train_densify_counts.argtypes = [i, vp, C.c_size_t, C.POINTER(i), vp]
     L.mi_train_densify_apply.restype = i
     L.mi_train_densify_apply.argtypes = [i, C.POINTER(i), i, pp, pp, C.POINTER(i), C.POINTER(i), vp, vp, C.c_size_t, vp]
+    L.mi_cluster_workspace_bytes.restype = C.c_size_t
+    L.mi_cluster_workspace_bytes.argtypes = [i, i, i, i]
+    L.mi_cluster_core_distances.restype = i
+    L.mi_cluster_core_distances.argtypes = [i, i, i, vp, i, vp, vp, C.c_size_t, vp]
+    L.mi_cluster_mst.restype = i
+    L.mi_cluster_mst.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
+    L.mi_cluster_mst_rounds.restype = i
+    L.mi_cluster_mst_rounds.argtypes = []
+    L.mi_cluster_labels_host.restype = i
+    L.mi_cluster_labels_host.argtypes = [i, i, vp, vp, vp, i, d, i, vp, C.POINTER(i)]
     _lib = L
     return L
 
