@@ -36,6 +36,8 @@ __device__ __forceinline__ float rcp_refined(float x)
     const float r = __builtin_amdgcn_rcpf(x);
     return fmaf(fmaf(-x, r, 1.0f), r, r);
 }
+typedef short v4s16 __attribute__((ext_vector_type(4)));   // four bf16 operands of v_mfma_f32_16x16x16_bf16
+
 // min(0.99, t) for t >= -1 as ONE instruction: v_med3_f32.  fminf() on a value that comes out of a select costs two (hipcc
 // canonicalises it first, v_max_f32 x, x, because the kernel runs in IEEE mode); the result is the same operand either way.
 __device__ __forceinline__ float alpha_clamp(float t) { return __builtin_amdgcn_fmed3f(t, 0.99f, -1.0f); }
@@ -72,7 +74,7 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
     constexpr int NB = C / 16;   // 16-channel blocks of the dF contraction
     constexpr int F4 = C / 4;    // float4s per feature row
     constexpr int NK = (CHK * F4 + 63) / 64;  // float4 feature parts per lane and chunk
-    constexpr int MROW = 16;   // floats per row of the moment / field staging: 6 moments, then 8 fields
+    constexpr int MROW = 16;   // floats per row of the moment / field staging: first 6 moments as doubles (8 fit), then, in place, 8 float fields
     static_assert(CR == C || (C == 16 && (CR == 3 || CR == 0)), "padded layouts: RGB, or a partial 16-channel block");
     static_assert(CR != 0 || STRIDED, "a partial block is a block of a wider (or narrower) feature: its row stride is an argument");
     static_assert(!MASKGRAD || CR == 3, "the mask gradient belongs to the RGB (DEPTH variant) kernel");
@@ -412,7 +414,10 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
         v4f facc[NB];
 #pragma unroll
         for (int nb = 0; nb < NB; nb++) facc[nb] = (v4f){0.f, 0.f, 0.f, 0.f};
-        v4f macc = (v4f){0.f, 0.f, 0.f, 0.f};
+        // u is split into its upper 18 significant bits and the 6 below them: both products with Phi (dyadics of at most six bits) are
+        // exact, so a row that blends into one or two pixels next to its centre loses nothing before the shift of step 6 cancels the
+        // moments.  The lower part and Phi fit bf16 exactly: one 16-pixel bf16 MFMA per four steps carries it.
+        v4f macc = (v4f){0.f, 0.f, 0.f, 0.f}, mlo = (v4f){0.f, 0.f, 0.f, 0.f};
         {
             const float4* wrow = reinterpret_cast<const float4*>(my_wa + n16 * WROW + 16 * kq);
             const float4* urow = reinterpret_cast<const float4*>(my_ua + n16 * WROW + 16 * kq);
@@ -422,6 +427,7 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
                 const float wa[4] = {wv.x, wv.y, wv.z, wv.w};
                 const float4 uv = urow[s4];
                 const float ua[4] = {uv.x, uv.y, uv.z, uv.w};
+                v4s16 ul4, ph4;
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
                     const int s = 4 * s4 + t;
@@ -430,8 +436,12 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
                         facc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[t], dLT[nb][s], facc[nb], 0, 0, 0);
                     const float x = (float)(s & 7) - 3.5f;
                     const float phi = fmaf(x, fmaf(x, phR, phQ[s >> 3]), phP[s >> 3]);
-                    macc = __builtin_amdgcn_mfma_f32_16x16x4f32(ua[t], phi, macc, 0, 0, 0);
+                    const float uh = __uint_as_float(__float_as_uint(ua[t]) & 0xFFFFFFC0u);
+                    macc = __builtin_amdgcn_mfma_f32_16x16x4f32(uh, phi, macc, 0, 0, 0);
+                    ul4[t] = (short)(__float_as_uint(ua[t] - uh) >> 16);
+                    ph4[t] = (short)(__float_as_uint(phi) >> 16);
                 }
+                mlo = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(ul4, ph4, mlo, 0, 0, 0);   // k = 4 kq + t: pixel 16 kq + 4 s4 + t
             }
         }
         // ---- 6. outputs.  Result layout: lane l holds column n16 of rows 4*kq + r.  Every atomic below is issued
@@ -456,34 +466,36 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
                 }
             }
         }
-        // (a separate, unconditional loop: with the store inside the loop above and guarded by n16 < 8, hipcc clones the
-        // atomics into both arms of the guard -- twice the memory instructions, and a count that depends on the path)
+        // Moment j of row 4 kq + r as a double, upper and lower part added exactly: eight doubles fill the row's MROW floats, columns
+        // 6 and 7 are zeros, columns 8 .. 15 are not stored.  (A loop of its own: with this guarded store inside the loop above, hipcc
+        // clones that loop's atomics into both arms of the guard -- twice the memory instructions, and a count that depends on the path.)
 #pragma unroll
-        for (int r = 0; r < 4; r++) my_mom[(4 * kq + r) * MROW + n16] = macc[r];
+        for (int r = 0; r < 4; r++)
+            if (n16 < 8) reinterpret_cast<double*>(my_mom + (4 * kq + r) * MROW)[n16] = (double)macc[r] + (double)mlo[r];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         // moments -> fields: lane = row (16 lanes) rewrites its my_mom row in place, then the wave adds the rows
         // to the packed per-Gaussian records: lane -> (row = l / 8 (+8), field = l % 8), 32 contiguous bytes per row
         {
             if (lane < 16) {
                 const int row = lane;
-                const float4 m0 = reinterpret_cast<const float4*>(my_mom + row * MROW)[0];
-                const float4 m1 = reinterpret_cast<const float4*>(my_mom + row * MROW)[1];
-                const float M0 = m0.x, M1 = m0.y, M2 = m0.z, M3 = m0.w, M4 = m1.x, M5 = m1.y;
+                const double* md = reinterpret_cast<const double*>(my_mom + row * MROW);
+                const double M0 = md[0], M1 = md[1], M2 = md[2], M3 = md[3], M4 = md[4], M5 = md[5];
                 const float ca = -2.f * mine.q0.z, cb = -mine.q0.w, cc = -2.f * mine.q1.x, op = mine.q1.y;
-                const float gx = mine.q0.x - cxq, gy = mine.q0.y - cyq;
+                // the shift to the Gaussian's centre in binary64: its three terms cancel (a centre 0.3 px from a lone pixel: 200 : 1)
+                const double gx = (double)mine.q0.x - (double)cxq, gy = (double)mine.q0.y - (double)cyq;
                 // dx = gx - x', dy = gy - y'
-                const float Sdx = gx * M0 - M1;
-                const float Sdy = gy * M0 - M2;
-                const float Sdxx = gx * gx * M0 - 2.f * gx * M1 + M3;
-                const float Sdxy = gx * gy * M0 - gx * M2 - gy * M1 + M4;
-                const float Sdyy = gy * gy * M0 - 2.f * gy * M2 + M5;
+                const float Sdx = (float)(gx * M0 - M1);
+                const float Sdy = (float)(gy * M0 - M2);
+                const float Sdxx = (float)(gx * gx * M0 - 2. * gx * M1 + M3);
+                const float Sdxy = (float)(gx * gy * M0 - gx * M2 - gy * M1 + M4);
+                const float Sdyy = (float)(gy * gy * M0 - 2. * gy * M2 + M5);
                 float4 o0, o1;
                 o0.x = -ddelx_dx * (ca * Sdx + cb * Sdy);  // dL_dmean2D.x
                 o0.y = -ddely_dy * (cc * Sdy + cb * Sdx);  // dL_dmean2D.y
                 o0.z = -0.5f * Sdxx;                       // dL_dconic.x
                 o0.w = -0.5f * Sdxy;                       // dL_dconic.y
                 o1.x = -0.5f * Sdyy;                       // dL_dconic.w
-                o1.y = M0 * __builtin_amdgcn_rcpf(op);     // dL_dopacity = sum G dL_dalpha
+                o1.y = (float)M0 * __builtin_amdgcn_rcpf(op);     // dL_dopacity = sum G dL_dalpha
                 o1.z = 0.f;
                 o1.w = 0.f;
                 reinterpret_cast<float4*>(my_mom + row * MROW)[0] = o0;

@@ -1,9 +1,10 @@
 """Independent dense PyTorch (float64, autograd) re-derivation of the rasterizer's math.
 
-Used ONLY to pin the CPU oracle (tests/test_oracle_*.py): the reference ships no tests or golden
+Pins the CPU oracle (tests/test_oracle_*.py): the reference ships no tests or golden
 vectors, so the oracle's forward AND its hand-written backward are checked against
 this autograd implementation, which shares no code with oracle/ and is built from the formulas of
-the reference's own Python helpers:
+the reference's own Python helpers.  With reference_quirks=True it is also the float64 reference the HIP
+kernels are held to per pixel and per Gaussian row on the designed edge scenes (tests/raster_edge_ref.py):
 
 * SH evaluation      -- utils/sh_utils.py:57-112 (eval_sh), constants :24-51
 * R from quaternion  -- utils/general_utils.py:78-99 (build_rotation), Sigma = (RS)(RS)^T
@@ -58,13 +59,27 @@ def build_rotation(q):
 
 def render_dense(means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, tanfovx, tanfovy, *,
                  scales=None, rotations=None, cov3D_precomp=None, colors_precomp=None, shs=None, sh_degree=0,
-                 scale_modifier=1.0, means2D_offset=None, mask=None, helpers=None):
+                 scale_modifier=1.0, means2D_offset=None, mask=None, helpers=None, dt=torch.float64,
+                 reference_quirks=False):
     """`helpers`: optional tests/reference_helpers.ReferenceHelpers -- SH evaluation, scaling-rotation matrix and the
     projective transform are then the REFERENCE's own Python functions (imported from /root/reference/utils), not the
-    restatements above.  All tensor inputs float64.  viewmatrix/projmatrix are the reference's transposed matrices
+    restatements above.  All tensor inputs of dtype `dt` (float64 by default; float32 gives the same expression evaluated in
+    float32 throughout, one more rounding order of the same function for tests/raster_edge_ref.py).
+
+    `reference_quirks=True` restates two places where the reference's hand-written backward is NOT the derivative of its forward
+    (the default, False, differentiates the forward exactly):
+    * CF/cuda_rasterizer/backward.cu:175-176, 262-264: for a centre beyond the 1.3 tan(fov) clamp, x_grad_mul / y_grad_mul is 0 AND
+      the clamped t.x / t.y enters dL/dt.z as a constant -- the clamped value is detached altogether, although lim * t.z depends on
+      t.z.
+    * CF/cuda_rasterizer/backward.cu:499, 540-554: alpha = min(0.99, opacity * G) is differentiated as if the min were not
+      there -- a straight-through clamp.
+
+    Further items for the decision margins of tests/raster_edge_ref.py, detached; the (P, N) ones in list order (out["order"]),
+    the (P,) ones in input order: raw_alpha = opacity * exp(power), power, member (the rect-membership mask), stop_value
+    = T (1 - alpha) of the stop test, alive, power_terms (the sum of the magnitudes of the three terms of power), weights, alpha_eff; sh_pre_clamp = sh_val + 0.5 (None with precomputed colours),
+    txtz, tytz, view_z, tiles_touched, colors.  viewmatrix/projmatrix are the reference's transposed matrices
     (row-vector convention: p_hom = [x,y,z,1] @ M).  Returns dict(color (C,H,W), radii, mask, depth,
     n_contrib, final_T)."""
-    dt = torch.float64
     P = means3D.shape[0]
     ones = torch.ones(P, 1, dtype=dt)
     hom = torch.cat([means3D, ones], 1)
@@ -93,8 +108,12 @@ def render_dense(means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, t
     focal_y = H / (2.0 * tanfovy)
     tx, ty, tz = p_view[:, 0], p_view[:, 1], p_view[:, 2]
     limx, limy = 1.3 * tanfovx, 1.3 * tanfovy
-    txc = torch.clamp(tx / tz, -limx, limx) * tz
-    tyc = torch.clamp(ty / tz, -limy, limy) * tz
+    txtz, tytz = tx / tz, ty / tz
+    txc = torch.clamp(txtz, -limx, limx) * tz
+    tyc = torch.clamp(tytz, -limy, limy) * tz
+    if reference_quirks:   # backward.cu:175-176, 262-264: a clamped t.x / t.y is a constant, also with respect to t.z
+        txc = torch.where((txtz < -limx) | (txtz > limx), txc.detach(), txc)
+        tyc = torch.where((tytz < -limy) | (tytz > limy), tyc.detach(), tyc)
     zero = torch.zeros_like(tz)
     J = torch.stack([focal_x / tz, zero, -(focal_x * txc) / (tz * tz),
                      zero, focal_y / tz, -(focal_y * tyc) / (tz * tz),
@@ -126,13 +145,15 @@ def render_dense(means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, t
     visible = visible & (det != 0) & ((rmaxx - rminx) * (rmaxy - rminy) > 0)
     radii = torch.where(visible, radius, torch.zeros_like(radius)).to(torch.int32)
 
+    sh_pre = None
     if colors_precomp is not None:
         colors = colors_precomp
     else:
         d = means3D - campos[None]
         d = d / d.norm(dim=1, keepdim=True)
         sh_val = eval_sh(sh_degree, shs, d) if helpers is None else helpers.eval_sh(sh_degree, shs, d)
-        colors = torch.clamp_min(sh_val + 0.5, 0.0)
+        sh_pre = sh_val + 0.5
+        colors = torch.clamp_min(sh_pre, 0.0)
 
     # order: (depth, index) ascending == the (tile|depth) radix sort restricted to any one tile
     depth32 = p_view[:, 2].detach().to(torch.float32)   # keys use fp32 depth bits
@@ -146,7 +167,12 @@ def render_dense(means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, t
     dx = px[o, None] - pixx[None]
     dy = py[o, None] - pixy[None]
     power = -0.5 * (conic_a[o, None] * dx * dx + conic_c[o, None] * dy * dy) - conic_b[o, None] * dx * dy
-    alpha = torch.clamp_max(opacities.reshape(-1)[o, None] * torch.exp(power), 0.99)
+    power_terms = (0.5 * (conic_a[o, None] * dx * dx + conic_c[o, None] * dy * dy) + (conic_b[o, None] * dx * dy).abs()).detach()
+    raw = opacities.reshape(-1)[o, None] * torch.exp(power)
+    if reference_quirks:   # backward.cu:499, 540: the gradient passes min(0.99, .) unchanged
+        alpha = raw + (torch.clamp_max(raw, 0.99) - raw).detach()
+    else:
+        alpha = torch.clamp_max(raw, 0.99)
     member = (visible[o, None] & (tilex[None] >= rminx[o, None]) & (tilex[None] < rmaxx[o, None])
               & (tiley[None] >= rminy[o, None]) & (tiley[None] < rmaxy[o, None]))
     ok = member & (power <= 0) & (alpha >= 1.0 / 255.0)
@@ -154,7 +180,8 @@ def render_dense(means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, t
     one_minus = 1.0 - A
     T_incl = torch.cumprod(one_minus, 0)
     T_excl = torch.cat([torch.ones(1, T_incl.shape[1], dtype=dt), T_incl[:-1]], 0)
-    stop = ok & ((T_excl * one_minus).detach() < 0.0001)
+    stop_value = (T_excl * one_minus).detach()
+    stop = ok & (stop_value < 0.0001)
     alive = (torch.cumsum(stop.to(torch.int64), 0) == 0)     # inclusive: the stopping Gaussian is not blended
     Aeff = torch.where(alive, A, torch.zeros_like(A))
     T_incl = torch.cumprod(1.0 - Aeff, 0)
@@ -169,4 +196,8 @@ def render_dense(means3D, opacities, viewmatrix, projmatrix, campos, bg, W, H, t
     # n_contrib: 1-based position within the TILE list is tile-dependent; expose the contributing matrix instead
     out["contrib"] = (Aeff > 0)
     out["order"] = order
+    out.update(raw_alpha=raw.detach(), power=power.detach(), power_terms=power_terms, member=member, stop_value=stop_value, alive=alive,
+               weights=wgt.detach(), alpha_eff=Aeff.detach(), sh_pre_clamp=None if sh_pre is None else sh_pre.detach(),
+               txtz=txtz.detach(), tytz=tytz.detach(), view_z=p_view[:, 2].detach(), colors=colors.detach(),
+               tiles_touched=torch.where(visible, (rmaxx - rminx) * (rmaxy - rminy), torch.zeros_like(radius)).to(torch.int64))
     return out
