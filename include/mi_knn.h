@@ -34,12 +34,15 @@ int mi_knn_build(int M, const float* ref, void* workspace, size_t workspace_byte
  *   query == NULL : the queries ARE the references (N is ignored, M rows are written, row i = reference i).
  *                   exclude_self != 0 leaves the point itself out of its own list.
  *   query [N,3]   : arbitrary points; exclude_self is ignored.
- * idx [rows,K] int64 (reference indices; -1 where fewer than K references exist), dist2 [rows,K] squared distances. */
+ * idx [rows,K] int64 (reference indices; -1 where fewer than K references exist), dist2 [rows,K] squared distances
+ * (+inf in the columns padded with -1).  A squared distance that overflows binary32 is +inf and still names its
+ * reference: such neighbours come last, by index. */
 int mi_knn_query(int N, const float* query, int M, const void* workspace, int K, int exclude_self,
                  int64_t* idx, float* dist2, void* stream);
 
 /* distCUDA2: out[i] = mean of the squared distances from point i to its 3 nearest OTHER points
- * (simple_knn.cu:145-183).  Builds its own index in `workspace` (>= mi_knn_workspace_bytes(P)). */
+ * (simple_knn.cu:145-183); +inf where there are fewer than 3 other points.  Builds its own index in `workspace`
+ * (>= mi_knn_workspace_bytes(P)). */
 int mi_knn_mean_dist2(int P, const float* points, void* workspace, size_t workspace_bytes, float* out, void* stream);
 
 #ifdef __cplusplus

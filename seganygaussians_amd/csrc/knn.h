@@ -254,7 +254,9 @@ __device__ __forceinline__ float box_dist2(const KnnBox& b, float px, float py, 
     return dx * dx + dy * dy + dz * dz;
 }
 
-// Best-K list in registers, ascending by (distance, index).
+// Best-K list in registers, ascending by (distance, index).  An empty slot is (+inf, 0xffffffff): it sorts after every candidate,
+// also after one whose squared distance overflows to +inf (finite coordinates 2e19 apart are enough), which ties with the empty
+// slots on distance and wins on index.  With a finite initial distance such a candidate was never admitted and the row kept -1.
 template <int K>
 struct KBest {
     float d[K];
@@ -263,7 +265,7 @@ struct KBest {
     {
 #pragma unroll
         for (int j = 0; j < K; j++) {
-            d[j] = 3.402823466e38f;
+            d[j] = __builtin_huge_valf();
             id[j] = 0xffffffffu;
         }
     }
