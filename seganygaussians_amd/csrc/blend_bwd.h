@@ -1,32 +1,19 @@
-// blend_bwd.h -- per-tile back-to-front gradient pass.
+// blend_bwd.h -- the mask-only tile backward: dL_dmask of the mask-only render pair (mi_rast_mask_backward).
 //
-// Restates renderCUDA<C> backward (CF/cuda_rasterizer/backward.cu:399-559); MASKGRAD adds the DEPTH
-// variant's dL_dmask (DEPTH/cuda_rasterizer/backward.cu:457,516); C==0 is the mask-only pair
-// (DEPTH/cuda_rasterizer/backward.cu:568-660).
+// Restates the backward of DEPTH/cuda_rasterizer/backward.cu:568-660: one workgroup per tile, one wave per quadrant, walking the
+// tile's blend list back to front in batches of ROWS records.  Every other gradient -- colours, the six geometric fields, the DEPTH
+// variant's mask gradient beside them -- is the wave-per-quadrant kernel's (blend_bwd_wave.h); this file computes none of them.
 //
-// What is different from the reference, by design (all float-path, tolerance-checked):
-//  * The per-channel recurrence  accum_rec[ch] = last_alpha*last_color[ch] + (1-last_alpha)*accum_rec[ch]
-//    followed by  dL_dalpha += (c[ch]-accum_rec[ch])*dL_dpixel[ch]  (backward.cu:517-522) is algebraically
-//    dL_dalpha = S_k - R_k with  S_k = <c_k, dL_dpixel>  and the SCALAR recurrence
-//    R_k = last_alpha*S_{k+1} + (1-last_alpha)*R_{k+1}.  That removes 2C of the 3C per-pair flops and 2C live
-//    registers per pixel (accum_rec, last_color).
-//  * The reference issues C+6 float atomicAdds per contributing pixel-Gaussian pair (backward.cu:525-556).
-//    Measured on MI355X (tools/atomic_bench.hip) the L2 executes ~10 G atomic LINE operations / s (one per
-//    128-B line an instruction touches, ~20 G/s for scattered dwords) -- at ~10^9 pair atomics per view that
-//    alone would be > 50 ms.  Here every gradient is reduced three times before it reaches HBM:
-//      1. over the 64 pixels of a wave: blend weights w[g][pixel] of up to SLOTS contributing Gaussians are
-//         parked in LDS, then the wave switches to a lane = channel layout (dL_dpixel held transposed in
-//         registers) and each lane sums w*dL over the pixels (the dF = W^T * dL_dpix contraction); the 6
-//         geometric fields (+mask) are quad-reduced with DPP, parked, and finished by lanes [4f, 4f+3];
-//      2. over the 4 waves of the tile: LDS float atomics (ds_add_f32) into per-entry accumulator rows shared
-//         by the workgroup;
-//      3. one flush per batch: touched rows go to HBM as ONE 128-B atomic per (tile, Gaussian) for the C=32
-//         channels plus ONE 32-B atomic into a packed per-Gaussian record {mean2D.xy, conic.xyw, opacity,
-//         mask} (unpacked later by the streaming geometry-backward kernel).
-//  * bg_dot_dpixel is hoisted out of the pair loop (backward.cu:533-535 recomputes it per pair).
-//  * The tile only walks entries below max_pixel(n_contrib) (the reference walks from the end of the range
-//    and skips, backward.cu:485-487), each wave only those below ITS quadrant's maximum, and entries are
-//    culled per quadrant exactly as in the forward (cull.h); features are staged for survivors only.
+// What is different from the reference, by design (float path, tolerance-checked):
+//  * The reference issues one float atomicAdd per contributing pixel-Gaussian pair.  Here the gradient is reduced three times before
+//    it reaches HBM:
+//      1. over the 64 pixels of a wave: w * dL_dout_mask is quad-reduced with DPP and its 16 partials parked in LDS for up to SLOTS
+//         contributing Gaussians; lanes 0..3 finish the sums;
+//      2. over the 4 waves of the tile: LDS float atomics into the batch's per-record accumulator rows;
+//      3. one flush per batch: touched rows go to HBM as one atomic per (tile, Gaussian) into field 6 of the packed per-Gaussian
+//         record {mean2D.xy, conic.xyw, opacity, mask, pad} (unpack_mask_kernel reads it).
+//  * The tile only walks entries below max_pixel(n_contrib) (the reference walks from the end of the range and skips), each wave only
+//    those below ITS quadrant's maximum, and entries are culled per quadrant exactly as in the forward (cull.h).
 #pragma once
 
 #include "blend_fwd.h"
@@ -35,42 +22,27 @@
 
 namespace mirast {
 
-constexpr int SLOTS = 4;     // contributing Gaussians parked per wave before a transposed flush
+constexpr int SLOTS = 4;     // contributing Gaussians parked per wave before a flush
 constexpr int NFIELD = 8;    // packed record: mean2D.x, mean2D.y, conic.x, conic.y, conic.w, opacity, mask, pad
-constexpr int ROWS = 128;    // survivor rows (features + gradient accumulators) resident in LDS at a time
+constexpr int ROWS = 128;    // blend-list records (+ their gradient accumulators) resident in LDS at a time
 
-template <int C, bool MASKGRAD, bool XEXP = false>
-__global__ void __launch_bounds__(256) blend_bwd_kernel(
+template <bool XEXP>
+__global__ void __launch_bounds__(256) mask_bwd_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ blend_list, const BlendRec* __restrict__ index_rec,
-    const uint32_t* __restrict__ tile_nsurv,
-    int W, int H, const float* __restrict__ bg_color, const float* __restrict__ colors,
-    const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels,
-    const float* __restrict__ dL_dout_mask, float* __restrict__ gpack /*[P,8] packed field gradients*/,
-    float* __restrict__ dL_dcolors)
+    const uint32_t* __restrict__ tile_nsurv, int W, int H, const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib,
+    const float* __restrict__ dL_dout_mask, float* __restrict__ gpack /*[P,8] packed field gradients*/)
 {
-    constexpr bool WIDE = (C >= 32);           // transposed LDS reduction for the colour channels
-    constexpr bool GEO = (C > 0);              // geometric gradients exist (not the mask-only pair)
-    constexpr int ROW = FeatStage<C>::ROW;
-    constexpr int NH = WIDE ? (64 / C) : 1;    // lane groups over pixels in the transposed layout (C=32: 2, C=64: 1)
-    constexpr int PPL = WIDE ? (64 / NH) : 1;  // pixels summed per lane in the transposed layout
-    static_assert(!WIDE || C == 32 || C == 64, "wide path supports C = 32 or 64");
-    constexpr int GC = C > 0 ? C : 1;
-
+    constexpr int MASK_FIELD = 6;
     __shared__ uint32_t s_id[ROWS];
     __shared__ float2 s_xy[ROWS];
     __shared__ float4 s_co[ROWS];
     __shared__ uint32_t s_pm[ROWS];
-    __shared__ float4 s_feat4[(C > 0 ? ROWS * ROW / 4 : 1)];
-    __shared__ float s_gcol[WIDE ? 1 : ROWS * GC];  // per-entry colour gradient shared by the 4 waves (narrow path)
     __shared__ float4 s_gfld4[ROWS * NFIELD / 4];  // per-entry packed field gradients
     __shared__ uint32_t s_touched[ROWS];
-    __shared__ float4 s_w4[WIDE ? 4 * SLOTS * 64 / 4 : 1];
     __shared__ float4 s_f4[4 * SLOTS * NFIELD * 16 / 4];  // quad-partials of the fields
     __shared__ int s_slot_row[4 * SLOTS];
     __shared__ int s_maxc;
-    float* s_feat = reinterpret_cast<float*>(s_feat4);
     float* s_gfld = reinterpret_cast<float*>(s_gfld4);
-    float* s_w = reinterpret_cast<float*>(s_w4);
     float* s_f = reinterpret_cast<float*>(s_f4);
 
     const int tid = threadIdx.x;
@@ -82,7 +54,6 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
     const uint32_t pix_id = W * py + px;
     const float pixfx = (float)px, pixfy = (float)py;
     const bool inside = px < (uint32_t)W && py < (uint32_t)H;
-    const size_t HW = (size_t)H * W;
 
     const uint2 range = ranges[tile];
     const int last_contributor = inside ? (int)n_contrib[pix_id] : 0;
@@ -101,96 +72,29 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
     const int NS = (int)tile_nsurv[tile];
     const uint32_t* lst = blend_list + range.x;   // four-byte entries; list_record (binning.h) gathers the geometry record of one
 
-    const float T_final = inside ? final_Ts[pix_id] : 0;
-    float T = T_final;
+    float T = inside ? final_Ts[pix_id] : 0;
+    // (clamped address + select: no branch)
+    const float dLm = dL_dout_mask[inside ? pix_id : 0];
+    const float dL_dout_mask_i = inside ? dLm : 0.f;
 
-    // pixel-major gradient of this lane's pixel (clamped address + select: no per-channel branches)
-    const size_t pix_safe = inside ? pix_id : 0;
-    float dL_dpixel[GC];
-    float bg_dot_dpixel = 0;
-#pragma unroll
-    for (int ch = 0; ch < C; ch++) {
-        const float v = dL_dpixels[ch * HW + pix_safe];
-        dL_dpixel[ch] = inside ? v : 0.f;
-        bg_dot_dpixel += bg_color[ch] * dL_dpixel[ch];
-    }
-    float dL_dout_mask_i = 0.f;
-    if constexpr (MASKGRAD) {
-        const float v = dL_dout_mask[pix_safe];
-        dL_dout_mask_i = inside ? v : 0.f;
-    }
-
-    // channel-major (transposed) gradient: lane -> channel n, pixel group h
-    float dLT[WIDE ? PPL : 1];
-    const int tn = WIDE ? (lane % GC) : 0, th = WIDE ? (lane / GC) : 0;
-    if constexpr (WIDE) {
-#pragma unroll
-        for (int p = 0; p < PPL; p++) {
-            const int l = th * PPL + p;  // pixel (lane index) inside this wave's quadrant
-            const uint32_t x = qx0 + (l & 7), y = qy0 + (l >> 3);
-            const bool in = x < (uint32_t)W && y < (uint32_t)H;
-            const float v = dL_dpixels[tn * HW + (in ? (size_t)W * y + x : 0)];
-            dLT[p] = in ? v : 0.f;
-        }
-    }
-
-    float last_alpha = 0.f, S_last = 0.f, Rrec = 0.f;
-    const float ddelx_dx = 0.5 * W;  // backward.cu:460-461
-    const float ddely_dy = 0.5 * H;
     int nslots = 0;  // wave-uniform
-    float* my_w = s_w + wave * SLOTS * 64;
     float* my_f = s_f + wave * SLOTS * NFIELD * 16;
     int* my_slot_row = s_slot_row + wave * SLOTS;
 
     // Finish the per-wave reductions of the parked Gaussians and add them to the tile's LDS accumulators.
-    // Unrolled over the slots so that the LDS reads of all parked rows are in flight together.
     auto flush = [&]() {
         // LDS rows written by this wave's own lanes: wave-local, no workgroup barrier needed
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         const int n = __builtin_amdgcn_readfirstlane(nslots);
-        if constexpr (WIDE) {
-            float sum[SLOTS];
-#pragma unroll
-            for (int s = 0; s < SLOTS; s++) {
-                sum[s] = 0.f;
-                if (s < n) {
-                    const float4* wrow = reinterpret_cast<const float4*>(my_w + s * 64 + th * PPL);
-                    float sum0 = 0.f, sum1 = 0.f;
-#pragma unroll
-                    for (int p4 = 0; p4 < PPL / 4; p4++) {
-                        const float4 wv = wrow[p4];
-                        sum0 = fmaf(wv.x, dLT[4 * p4 + 0], sum0);
-                        sum1 = fmaf(wv.y, dLT[4 * p4 + 1], sum1);
-                        sum0 = fmaf(wv.z, dLT[4 * p4 + 2], sum0);
-                        sum1 = fmaf(wv.w, dLT[4 * p4 + 3], sum1);
-                    }
-                    sum[s] = sum0 + sum1;
-                }
-            }
+        if (lane < 4) {   // one quad at work: lane l sums partials [4 l, 4 l + 4)
 #pragma unroll
             for (int s = 0; s < SLOTS; s++) {
                 if (s < n) {
-                    // LDS float atomics cost ~1.5 LDS cycles per lane (measured: they were 60% of this kernel's LDS
-                    // time), while a contiguous 128-B global atomic is ONE L2 line operation: send each wave's
-                    // channel sums straight to HBM.
-                    float v = sum[s];
-                    if constexpr (NH == 2) v += __shfl_xor(v, 32, 64);
-                    if (th == 0) atomicAdd(&dL_dcolors[(size_t)s_id[my_slot_row[s]] * C + tn], v);
-                }
-            }
-        }
-        // fields: lane l < 4*NQ handles field fi = l/4, partials [4*(l%4), +4)
-        constexpr int NQ = GEO ? (MASKGRAD ? 7 : 6) : 1;  // quads at work (mask-only pair: field 6 only)
-        if (lane < 4 * NQ) {
-            const int fi = GEO ? (lane >> 2) : 6;
-#pragma unroll
-            for (int s = 0; s < SLOTS; s++) {
-                if (s < n) {
-                    const float4 v = reinterpret_cast<const float4*>(my_f + (s * NFIELD + fi) * 16)[lane & 3];
+                    const float4 v = reinterpret_cast<const float4*>(my_f + (s * NFIELD + MASK_FIELD) * 16)[lane & 3];
                     float sum = (v.x + v.y) + (v.z + v.w);
                     sum += dpp_mov<0xB1>(sum);  // quad_perm [1,0,3,2]
                     sum += dpp_mov<0x4E>(sum);  // quad_perm [2,3,0,1]
-                    if ((lane & 3) == 0) atomicAdd(&s_gfld[my_slot_row[s] * NFIELD + fi], sum);
+                    if ((lane & 3) == 0) atomicAdd(&s_gfld[my_slot_row[s] * NFIELD + MASK_FIELD], sum);
                 }
             }
         }
@@ -218,25 +122,9 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
             s_id[tid] = cur.id;
             s_pm[tid] = cur.pm;
             s_touched[tid] = 0u;
-            if constexpr (C > 0 && !WIDE) {
-#pragma unroll
-                for (int ch = 0; ch < C; ch++) s_feat[tid * ROW + ch] = colors[(size_t)cur.id * C + ch];
-            }
         }
         if (tid < ROWS && b0 + ROWS + tid < NS) cur = list_record(lst, index_rec, NS - 1 - (b0 + ROWS + tid));
-        // ---- B: features of this batch; clear the tile accumulators
-        if constexpr (WIDE) {
-            constexpr int F4 = C / 4;
-#pragma unroll
-            for (int k = 0; k < ROWS * F4 / BATCH; k++) {
-                const int q = tid + BATCH * k;
-                const int g = q / F4, part = q % F4;
-                if (g < nr)
-                    s_feat4[g * F4 + part] = reinterpret_cast<const float4*>(colors + (size_t)(lst[NS - 1 - (b0 + g)] & ID_MASK) * C)[part];
-            }
-        }
-        if constexpr (C > 0 && !WIDE)
-            for (int q = tid; q < nr * GC; q += BATCH) s_gcol[q] = 0.f;
+        // ---- B: clear the tile accumulators
         for (int q = tid; q < nr * NFIELD; q += BATCH) s_gfld[q] = 0.f;
         __syncthreads();
 
@@ -266,47 +154,8 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
 
                 const float one_m_alpha_inv = __builtin_amdgcn_rcpf(1.f - alpha);
                 T = valid ? T * one_m_alpha_inv : T;
-                const float w = valid ? alpha * T : 0.f;  // dchannel_dcolor
-
-                if constexpr (!GEO) {
-                    park(6, w * dL_dout_mask_i);
-                } else {
-                    float S0 = 0.f, S1 = 0.f;
-#pragma unroll
-                    for (int ch = 0; ch < C; ch += 2) {
-                        S0 = fmaf(s_feat[r * ROW + ch], dL_dpixel[ch], S0);
-                        if (ch + 1 < C) S1 = fmaf(s_feat[r * ROW + ch + 1], dL_dpixel[ch + 1], S1);
-                    }
-                    const float S = S0 + S1;
-                    Rrec = valid ? (last_alpha * S_last + (1.f - last_alpha) * Rrec) : Rrec;
-                    float dL_dalpha = (S - Rrec) * T;
-                    S_last = valid ? S : S_last;
-                    last_alpha = valid ? alpha : last_alpha;
-                    dL_dalpha += (-T_final * one_m_alpha_inv) * bg_dot_dpixel;
-                    dL_dalpha = valid ? dL_dalpha : 0.f;
-
-                    const float dL_dG = cco.w * dL_dalpha;
-                    const float gdx = G * dx, gdy = G * dy;
-                    const float dG_ddelx = -gdx * cco.x - gdy * cco.y;
-                    const float dG_ddely = -gdy * cco.z - gdx * cco.y;
-                    park(0, dL_dG * dG_ddelx * ddelx_dx);   // dL_dmean2D.x
-                    park(1, dL_dG * dG_ddely * ddely_dy);   // dL_dmean2D.y
-                    park(2, -0.5f * gdx * dx * dL_dG);      // dL_dconic.x
-                    park(3, -0.5f * gdx * dy * dL_dG);      // dL_dconic.y
-                    park(4, -0.5f * gdy * dy * dL_dG);      // dL_dconic.w
-                    park(5, G * dL_dalpha);                 // dL_dopacity
-                    if constexpr (MASKGRAD) park(6, w * dL_dout_mask_i);
-                    if constexpr (WIDE) {
-                        my_w[__builtin_amdgcn_readfirstlane(nslots) * 64 + lane] = w;
-                    } else {
-                        // narrow path (C = 3): per-channel wave reduction, one lane adds to the tile accumulator
-#pragma unroll
-                        for (int ch = 0; ch < C; ch++) {
-                            const float gc = wave_sum(w * dL_dpixel[ch]);
-                            if (lane == 0) atomicAdd(&s_gcol[r * GC + ch], gc);
-                        }
-                    }
-                }
+                const float w = valid ? alpha * T : 0.f;  // dmask_out / dmask of this Gaussian
+                park(MASK_FIELD, w * dL_dout_mask_i);
                 if (lane == 0) my_slot_row[__builtin_amdgcn_readfirstlane(nslots)] = r;
                 nslots++;
                 if (nslots == SLOTS) flush();
@@ -315,20 +164,11 @@ __global__ void __launch_bounds__(256) blend_bwd_kernel(
         }
         __syncthreads();
 
-        // ---- D: one HBM atomic per touched (tile, Gaussian): C channels (128 B at C=32) + one packed 32-B record
-        if constexpr (C > 0 && !WIDE) {
-            constexpr int RPP = BATCH / GC > 0 ? BATCH / GC : 1;  // rows per pass
-            const int rr = tid / GC, ch = tid % GC;
-            if (rr < RPP)
-                for (int r = rr; r < nr; r += RPP)
-                    if (s_touched[r]) atomicAdd(&dL_dcolors[(size_t)s_id[r] * C + ch], s_gcol[r * GC + ch]);
-        }
+        // ---- D: one HBM atomic per touched (tile, Gaussian) into the packed record
         {
             const int rr = tid / NFIELD, f = tid % NFIELD;
-            constexpr int NF = GEO ? (MASKGRAD ? 7 : 6) : 7;
             for (int r = rr; r < nr; r += BATCH / NFIELD)
-                if (s_touched[r] && f < NF && (GEO || f == 6))
-                    atomicAdd(&gpack[(size_t)s_id[r] * NFIELD + f], s_gfld[r * NFIELD + f]);
+                if (s_touched[r] && f == MASK_FIELD) atomicAdd(&gpack[(size_t)s_id[r] * NFIELD + f], s_gfld[r * NFIELD + f]);
         }
     }
 }

@@ -9,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "binning.h"
@@ -29,11 +31,11 @@ using namespace mirast;
 namespace {
 
 // Mirrors CHECK_CUDA (CF/cuda_rasterizer/auxiliary.h:166-173): with debug set, synchronise after each
-// stage and surface the error; without it only launch errors are caught.
-#define STAGE_CHECK(name)                                                                              \
+// stage and surface the error; without it only launch errors are caught.  (c: the Call below.)
+#define STAGE_CHECK(c, name)                                                                           \
     do {                                                                                               \
         hipError_t _e = hipGetLastError();                                                             \
-        if (_e == hipSuccess && debug) _e = hipStreamSynchronize(stream);                              \
+        if (_e == hipSuccess && (c).debug) _e = hipStreamSynchronize((c).stream);                      \
         if (_e != hipSuccess)                                                                          \
             return fail(MI_RAST_ERR_HIP, std::string("[HIP ERROR] in stage ") + name + ": " + hipGetErrorString(_e)); \
     } while (0)
@@ -48,6 +50,9 @@ struct HostSync {
     hipEvent_t ev = nullptr;
     hipEvent_t ev2 = nullptr;
     bool ok = false;
+    // the words behind the R partial sums (binning.h: NR_*), as the host reads them and as the range scan addresses them
+    const int* words() const { return pinned + R_SLOTS * R_SLOT_STRIDE; }
+    int* words_dev() const { return pinned_dev + R_SLOTS * R_SLOT_STRIDE; }
     bool init()
     {
         if (ok) return true;
@@ -85,7 +90,7 @@ int current_device()
 std::atomic<bool> g_profile{false};
 struct ProfileEvents {
     hipEvent_t ev[MI_STAGE_COUNT][2];
-    bool created = false;
+    std::atomic<bool> created{false};   // read outside the mutex while another host thread's forward may be creating the events
     bool used[MI_STAGE_COUNT] = {};
 };
 ProfileEvents g_prof[MAX_DEVICES];
@@ -95,13 +100,13 @@ ProfileEvents* profile_events(int dev)
 {
     if (dev < 0) return nullptr;
     ProfileEvents& pe = g_prof[dev];
-    if (!pe.created) {
+    if (!pe.created.load(std::memory_order_acquire)) {
         std::lock_guard<std::mutex> lock(g_prof_mutex);
-        if (!pe.created) {
+        if (!pe.created.load(std::memory_order_relaxed)) {
             for (int i = 0; i < MI_STAGE_COUNT; i++)
                 for (int k = 0; k < 2; k++)
                     if (hipEventCreate(&pe.ev[i][k]) != hipSuccess) return nullptr;
-            pe.created = true;
+            pe.created.store(true, std::memory_order_release);
         }
     }
     return &pe;
@@ -181,7 +186,7 @@ struct ImgPtrs {
     uint32_t* tile_nsurv;   // per tile: blend-list entries the forward walked
     uint32_t* run_bounds;   // [9]: the blend kernels' XCD runs of tiles (common.h: XcdRuns): from the range scan (equal counts, or equal
                             // modelled work)
-    uint32_t longest_run;   // host copy of the longest of those runs (forward only: read from the pinned words at the ev2 wait)
+    int* words() const { return num_rendered + R_SLOTS * R_SLOT_STRIDE; }   // the words behind the R partial sums (binning.h: NR_*)
 };
 struct BinPtrs {
     uint2* entries;      // per overlap: {depth bits, Gaussian id | quadrant mask << 28}, bucketed by tile (unsorted inside a tile)
@@ -222,8 +227,7 @@ ImgPtrs img_from(char* base, int W, int H)
     m.tile_cursor = (uint32_t*)(base + off[MI_IMG_TILE_CURSOR]);
     m.num_rendered = (int*)(base + off[MI_IMG_NUM_RENDERED]);
     m.tile_nsurv = (uint32_t*)(base + off[MI_IMG_TILE_NSURV]);
-    m.run_bounds = reinterpret_cast<uint32_t*>(m.num_rendered + R_SLOTS * R_SLOT_STRIDE + NR_RUN_BOUNDS);
-    m.longest_run = 0;
+    m.run_bounds = reinterpret_cast<uint32_t*>(m.words() + NR_RUN_BOUNDS);
     return m;
 }
 BinPtrs bin_from(char* base, int R)
@@ -237,14 +241,11 @@ BinPtrs bin_from(char* base, int R)
     return b;
 }
 
-// One-time opt-in to > 64 KB of dynamic LDS (gfx950: 160 KB per workgroup), per device.
-std::atomic<bool> g_attr_set[MAX_DEVICES];
-std::mutex g_attr_mutex;
-
-// RGB (+ the DEPTH variant's mask / depth planes), or any multiple of 16 feature channels up to 256: wider features are blended
-// in channel blocks of 64 / 32 / 16 (every pass re-evaluates alpha and T; the contraction over channels is linear, so the
-// backward's per-block geometry gradients add up in the packed record).  The reference compiles ONE NUM_CHANNELS into its
-// kernels (CF/cuda_rasterizer/config_contrastive_f.h:15).
+// RGB (+ the DEPTH variant's mask / depth planes), or a feature of any width from 1 to MAX_CHANNELS (the reference compiles ANY ONE
+// NUM_CHANNELS into its kernels, CF/cuda_rasterizer/config_contrastive_f.h:15): blended in channel blocks of 64 / 32 / 16, the last one
+// possibly PARTIAL -- fewer real channels, zeros in the MFMA operands behind them, as RGB has always been rendered (3 of 16).  Every
+// pass re-evaluates alpha and T; the contraction over channels is linear, so the backward's per-block geometry gradients add up in the
+// packed record.
 constexpr int MAX_CHANNELS = 256;
 constexpr int MAX_CHANNEL_BLOCKS = MAX_CHANNELS / 16;
 // bytes of the geometry buffer's bwd_pack field: the packed per-Gaussian field gradients + the backward's work-queue counters (one set
@@ -253,12 +254,42 @@ inline size_t bwd_pack_bytes(int P)
 {
     return (size_t)(P > 0 ? P : 1) * 8 * sizeof(float) + MAX_CHANNEL_BLOCKS * 8 * XCD_QUEUE_STRIDE * sizeof(uint32_t);
 }
-// Any width from 1 to MAX_CHANNELS (the reference compiles ANY NUM_CHANNELS into its kernels, config_contrastive_f.h:15): blocks of
-// 64 / 32 / 16 channels, the last one possibly PARTIAL -- fewer than 16 real channels, zeros in the MFMA operands behind them, as
-// RGB has always been rendered (3 of 16).
 bool channels_supported(int c) { return c >= 1 && c <= MAX_CHANNELS; }
-// next block of a feature with `rem` channels left (rem < 16: a 16-channel block of which `rem` exist)
-int channel_block(int rem) { return rem >= 64 ? 64 : (rem >= 32 ? 32 : 16); }
+// One launch's share of a feature: channels [c0, c0 + real), blended by the kernel instantiation for `width` channels (real < width: PARTIAL)
+struct ChannelBlock { int c0, width, real; };
+// The one plan of all three blend passes: calls f(block) for the blocks of a `channels`-wide feature in order -- 64 channels while
+// that many are left, then halving down to `smallest`; what is left behind the last whole block is one partial block of `smallest`
+// (the forward: 32, 1 .. 31 channels of it real; the backwards and the profiling build's comparison forwards: 16).
+template <class F>
+void for_channel_blocks(int channels, int smallest, F&& f)
+{
+    for (int c0 = 0, width = 64; c0 < channels; c0 += width) {
+        while (width > smallest && channels - c0 < width) width >>= 1;
+        f(ChannelBlock{c0, width, std::min(width, channels - c0)});
+    }
+}
+
+// Run-time value -> compile-time constant: each calls the generic lambda f with a std::integral_constant whose ::value names the
+// kernel instantiation.  An arm no caller takes is closed with `if constexpr` inside f, so that it instantiates no kernel.
+template <class F>
+void with_bool(bool b, F&& f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <class F>
+void with_bools(bool a, bool b, F&& f)
+{
+    with_bool(a, [&](auto ka) { with_bool(b, [&](auto kb) { f(ka, kb); }); });
+}
+template <class F>
+void with_exp_mode(int xm, F&& f)   // common.h: ExpMode
+{
+    if (xm == EXP_HYBRID) f(std::integral_constant<int, EXP_HYBRID>{});
+    else if (xm == EXP_EXACT) f(std::integral_constant<int, EXP_EXACT>{});
+    else f(std::integral_constant<int, EXP_FAST>{});
+}
+
 // what mi_rast_forward and mi_rast_forward_reuse refuse alike
 int check_forward_args(int P, int channels, int width, int height, const float* colors_precomp, const float* mask)
 {
@@ -290,317 +321,428 @@ inline uint32_t longest_of(const int* bounds, uint32_t ntiles)
     return std::min(std::max(longest, (ntiles + 7u) >> 3), xcd_max_run(ntiles));
 }
 
-// Stages shared by forward and mask_forward: CF/cuda_rasterizer/rasterizer_impl.cu:246-317.
-int geometry_and_binning(mi_rast_resize_fn geometry_buffer, void* geometry_user, mi_rast_resize_fn binning_buffer,
-                         void* binning_user, mi_rast_resize_fn image_buffer, void* image_user, int P, int D, int M,
-                         int W, int H, const float* means3D, const float* shs, int colors_given,
-                         const float* opacities, const float* scales, const float* rotations,
-                         const float* cov3D_precomp, const ViewParams& vp, int prefiltered, int* radii, int debug,
-                         int flags, hipStream_t stream, GeomPtrs& geom, ImgPtrs& img, BinPtrs& bin, int* num_rendered)
-{
-    const int dev = current_device();
-    if (dev < 0) return fail(MI_RAST_ERR_HIP, "hipGetDevice failed (or device ordinal >= 64)");
-    HostSync& g_host_sync = g_host_sync_tl[dev];
-    size_t goff[MI_GEOM_NFIELDS], ioff[MI_IMG_NFIELDS];
-    const size_t geom_size = mi_rast_geometry_layout(P, goff);
-    char* geom_base = geometry_buffer(geom_size, geometry_user);
-    if (!geom_base) return fail(MI_RAST_ERR_ALLOC, "geometry buffer callback returned NULL");
-    geom = geom_from(geom_base, P);
-    const size_t img_size = mi_rast_image_layout(W, H, ioff);
-    char* img_base = image_buffer(img_size, image_user);
-    if (!img_base) return fail(MI_RAST_ERR_ALLOC, "image buffer callback returned NULL");
-    img = img_from(img_base, W, H);
+// What the stage and launch functions of one call share: the view, the stream, the caller's switches, the fields of the three buffers.
+struct Call {
+    ViewParams vp;
+    hipStream_t stream;
+    int debug, flags, P;
+    GeomPtrs geom;
+    ImgPtrs img;
+    BinPtrs bin;
+    uint32_t longest_run;   // of the XCD runs of tiles (a forward reads it at the ev2 wait, a reuse is handed it; 0: unknown): the forward blend's grid
+    uint32_t ntiles() const { return vp.grid_x * vp.grid_y; }
+    size_t HW() const { return (size_t)vp.W * vp.H; }   // floats of one image plane
+    bool xexp() const { return (flags & MI_RAST_FAST_EXP) == 0; }   // the device library's expf (common.h gauss_exp), the default
+    // the wave-per-quadrant forward kernels: common.h ExpMode
+    int exp_mode() const { return (flags & MI_RAST_FAST_EXP) ? EXP_FAST : (flags & MI_RAST_EXACT_EXP) ? EXP_EXACT : EXP_HYBRID; }
+};
 
-    int* cull_counter = geom.cull_counter;
-    if (prefiltered) HIP_TRY(hipMemsetAsync(cull_counter, 0, sizeof(int), stream));
-    const int ntiles = (int)(vp.grid_x * vp.grid_y);
-    if (P >= (1 << ID_BITS)) return fail(MI_RAST_ERR_INVALID, "more than 2^28 Gaussians");
-    if (vp.grid_x > 1023u || vp.grid_y > 2047u)
-        return fail(MI_RAST_ERR_INVALID, "image too large: more than 1023 tiles across or 2047 tiles down");
+// What the caller of mi_rast_forward / mi_rast_mask_forward hands to the stages before the blend
+struct FrontArgs {
+    mi_rast_resize_fn geometry_buffer, binning_buffer, image_buffer;
+    void *geometry_user, *binning_user, *image_user;
+    int D, M, colors_given, prefiltered;
+    const float *means3D, *shs, *opacities, *scales, *rotations, *cov3D_precomp;
+    int* radii;
+};
+
+// How the count and emit passes walk the tile grid (binning.h)
+struct BinPlan {
     // FULL lists (parity tests): images with more tiles than one launch of the full count / emit passes has LDS counters for are walked
     // in bands of tile rows by the host (grid_x + 2: the count pass keeps band_rows (+ 1) rows of an odd stride >= grid_x + 1)
-    const uint32_t band_rows = std::min<uint32_t>(vp.grid_y, std::max<uint32_t>(1u, (uint32_t)BIN_MAX_TILES / (vp.grid_x + 2u) - 1u));
-    const uint32_t nbands = (vp.grid_y + band_rows - 1) / band_rows;
+    uint32_t band_rows, nbands;
     // LEAN lists: <= MAX_BANDS device-side bands of lean_band_h tile rows, every workgroup of the count / emit passes in one of them
-    uint32_t lean_band_h = 1, lean_nbands = 1;
-    if (!band_geometry(vp.grid_x, vp.grid_y, SPAN_MAX_HEAD_WORDS, lean_band_h, lean_nbands))
-        return fail(MI_RAST_ERR_INVALID, "image too large for the banded binning passes (more than 24 bands of tile rows at this width)");
-    {
-        StageTimer t(stream, MI_STAGE_PREPROCESS);
-        HIP_TRY(hipMemsetAsync(img.num_rendered, 0, R_SLOTS * R_SLOT_STRIDE * sizeof(int), stream));
-        // (the per-tile entry totals are zeroed by the preprocess kernel's first threads; fewer Gaussians than tiles: by a fill)
-        if (P < ntiles) HIP_TRY(hipMemsetAsync(img.tile_cursor, 0, (size_t)ntiles * sizeof(uint32_t), stream));
-        // SH colours: the workgroup's coefficient rows are staged in LDS (geometry.h), 256 rows of 3 M + 4 floats
-        const size_t sh_lds = colors_given ? 0 : (size_t)256 * (3 * (size_t)M + 4) * sizeof(float);
-        if (sh_lds > 64 * 1024) return fail(MI_RAST_ERR_INVALID, "too many SH coefficients per Gaussian (at most 16: degree 3)");
-        hipLaunchKernelGGL(preprocess_fwd_kernel, dim3((P + 255) / 256), dim3(256), sh_lds, stream, P, D, M, means3D, scales,
-                           rotations, opacities, shs, geom.clamped, cov3D_precomp, colors_given, vp, radii,
-                           geom.means2D, geom.depths, geom.cov3D, geom.rgb, geom.conic_opacity, geom.tiles_touched,
-                           geom.depth_key, geom.index_rec, img.num_rendered, prefiltered, cull_counter, geom.band_bits, lean_band_h, lean_nbands,
-                           img.tile_cursor, (uint32_t)ntiles);
-    }
-    STAGE_CHECK("preprocess");
-    if (prefiltered) {
-        int culled = 0;
-        HIP_TRY(hipMemcpyAsync(&culled, cull_counter, sizeof(int), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (culled)
-            return fail(MI_RAST_ERR_INVALID, "Point is filtered although prefiltered is set. This shouldn't happen!");
-    }
-    if (!g_attr_set[dev].load(std::memory_order_acquire)) {
-        std::lock_guard<std::mutex> lock(g_attr_mutex);
-        if (!g_attr_set[dev].load(std::memory_order_relaxed)) {
-            const int max_lds = (int)((BIN_MAX_TILES + 11 * 1024 + 16) * sizeof(uint32_t));
-            HIP_TRY(hipFuncSetAttribute((const void*)bin_ranks_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)bin_ranks_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            HIP_TRY(hipFuncSetAttribute((const void*)bin_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-            // (160 KB per workgroup less the kernels' static words: the band plan)
-            HIP_TRY(hipFuncSetAttribute((const void*)bin_spans_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-            HIP_TRY(hipFuncSetAttribute((const void*)bin_spans_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-            HIP_TRY(hipFuncSetAttribute((const void*)tile_ranges_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (BIN_MAX_TILES_TOTAL + 1) * (int)sizeof(uint32_t)));
-            g_attr_set[dev].store(true, std::memory_order_release);
-        }
-    }
-    // R is known after the preprocess pass; the count pass stores its partial sums into the host's pinned
-    // buffer, and the host reads them while the scans run.
-    if (!g_host_sync.init()) return fail(MI_RAST_ERR_HIP, "cannot allocate pinned host buffer / event");
+    uint32_t lean_band_h, lean_nbands;
     // Full lists (the reference's point_list and full-list positions) are materialised on request -- the reference's
     // `debug` flag or MI_RAST_FULL_LISTS -- ; otherwise only the overlaps that pass the cull are listed.
-    const bool nocull = (flags & MI_RAST_NO_CULL) != 0;
-    const bool full = debug != 0 || nocull || (flags & MI_RAST_FULL_LISTS) != 0;
+    bool nocull, full;
     // full lists: <= 256 workgroups of 1024 threads, each a slice of the Gaussians (64-index chunks dealt round robin); lean lists:
     // workgroups dealt to the bands in proportion to the bands' Gaussian counts (binning.h: band_plan), at least one per band
-    const int nwg = full ? bin_workgroups(P) : std::min(BIN_LEAN_WG, (int)lean_nbands + (P + 1023) / 1024);
-    const size_t band_tiles = (size_t)band_rows * vp.grid_x;
-    const size_t bin_lds = ((size_t)((band_tiles + 3) & ~(size_t)3) + 3 * 1024 + 16) * sizeof(uint32_t);
-    {
-        // count pass over slices, scan over (tile, slice), scan over tiles -> ranges (binning.h)
-        StageTimer t(stream, MI_STAGE_TILE_SCAN);
-        const size_t cnt_lds = (size_t)(band_rows + 1) * count_grid_stride(vp.grid_x) * sizeof(int);
-        for (uint32_t b = 0; full && b < nbands; b++) {
-            const uint32_t by0 = b * band_rows, by1 = std::min(vp.grid_y, by0 + band_rows);
-            if (full)
-                hipLaunchKernelGGL(bin_count_kernel, dim3(nwg), dim3(BIN_THREADS), cnt_lds, stream, P, geom.index_rec, geom.depth_key,
-                                   img.tile_count, vp.grid_x, vp.grid_y, by0, by1, (const int*)img.num_rendered,
-                                   b == 0 ? g_host_sync.pinned_dev : (int*)nullptr);
-        }
-        if (!full)
-            hipLaunchKernelGGL(bin_spans_kernel<false>, dim3(nwg), dim3(1024), span_lds_bytes((size_t)lean_band_h * count_grid_stride(vp.grid_x)),
-                               stream, P, geom.index_rec, geom.depth_key, geom.band_bits, img.tile_count, img.tile_cursor, (const uint2*)nullptr, (uint2*)nullptr,
-                               vp.grid_x, vp.grid_y, lean_band_h, lean_nbands, (const int*)img.num_rendered, g_host_sync.pinned_dev);
-        HIP_TRY(hipEventRecord(g_host_sync.ev, stream));
-        // (one launch for both scans -- every workgroup scans its tiles over the slices, the last one to finish scans the totals
-        // behind a device-scope counter and agent-scope fences -- was built and measured in round 4: tile scan 0.058 -> 0.060 ms
-        // on cfg3; the fences and the serial tail inside the kernel cost more than the launch they save)
-        // full lists: scan over (tile, slice); lean lists: the count pass left the tile totals and every workgroup's offset itself
-        if (full)
-            hipLaunchKernelGGL(scan_partials_kernel, dim3((ntiles + 63) / 64), dim3(1024), 0, stream, ntiles, nwg,
-                               img.tile_count, img.tile_cursor);
-        const uint32_t run_cap = !(flags & MI_RAST_EQUAL_RUNS) ? (uint32_t)RUN_MODEL_CAP : 0u;
-        const uint32_t run_fix = (uint32_t)RUN_MODEL_FIX;
-        hipLaunchKernelGGL(tile_ranges_kernel, dim3(1), dim3(1024),
-                           ((size_t)std::min(ntiles, BIN_MAX_TILES_TOTAL) + 1) * sizeof(uint32_t), stream, ntiles, img.tile_cursor,
-                           img.ranges, img.num_rendered + R_SLOTS * R_SLOT_STRIDE, (const int*)img.num_rendered,
-                           g_host_sync.pinned_dev + R_SLOTS * R_SLOT_STRIDE, img.tile_consumed, img.tile_nsurv, img.run_bounds, run_cap, run_fix);
-    }
-    STAGE_CHECK("tile scan");
-    HIP_TRY(hipEventRecord(g_host_sync.ev2, stream));
-    // rasterizer_impl.cu:280-281: the host needs num_rendered to size the binning buffer.  We wait only for
-    // the copy (event), not for the work queued behind it.
-    HIP_TRY(hipEventSynchronize(g_host_sync.ev));
-    long long Rsum = 0;
-    for (int k = 0; k < R_SLOTS; k++) Rsum += g_host_sync.pinned[k * R_SLOT_STRIDE];
-    if (Rsum > 0x7fffffffll) return fail(MI_RAST_ERR_INVALID, "more than 2^31 tile overlaps");
-    const int R = (int)Rsum;
-    *num_rendered = R;
+    int nwg;
+};
+// (refuses what the passes cannot index, before any buffer is asked for or any work queued)
+int plan_binning(const Call& c, BinPlan& bp)
+{
+    const ViewParams& vp = c.vp;
+    if (c.P >= (1 << ID_BITS)) return fail(MI_RAST_ERR_INVALID, "more than 2^28 Gaussians");
+    if (vp.grid_x > 1023u || vp.grid_y > 2047u)
+        return fail(MI_RAST_ERR_INVALID, "image too large: more than 1023 tiles across or 2047 tiles down");
+    bp.band_rows = std::min<uint32_t>(vp.grid_y, std::max<uint32_t>(1u, (uint32_t)BIN_MAX_TILES / (vp.grid_x + 2u) - 1u));
+    bp.nbands = (vp.grid_y + bp.band_rows - 1) / bp.band_rows;
+    bp.lean_band_h = bp.lean_nbands = 1;
+    if (!band_geometry(vp.grid_x, vp.grid_y, SPAN_MAX_HEAD_WORDS, bp.lean_band_h, bp.lean_nbands))
+        return fail(MI_RAST_ERR_INVALID, "image too large for the banded binning passes (more than 24 bands of tile rows at this width)");
+    bp.nocull = (c.flags & MI_RAST_NO_CULL) != 0;
+    bp.full = c.debug != 0 || bp.nocull || (c.flags & MI_RAST_FULL_LISTS) != 0;
+    bp.nwg = bp.full ? bin_workgroups(c.P) : std::min(BIN_LEAN_WG, (int)bp.lean_nbands + (c.P + 1023) / 1024);
+    return MI_RAST_OK;
+}
 
-    size_t boff[MI_BIN_NFIELDS];
-    const size_t bin_size = mi_rast_binning_layout(R, boff);
-    char* bin_base = binning_buffer(bin_size, binning_user);
-    if (!bin_base) return fail(MI_RAST_ERR_ALLOC, "binning buffer callback returned NULL");
-    bin = bin_from(bin_base, R);
-    const bool verify = !full && (flags & MI_RAST_VERIFY_LISTS) != 0;
-    if (R > 0) {
-        if (verify) HIP_TRY(hipMemsetAsync(bin.entries, 0, (size_t)R * sizeof(uint2), stream));
-        {
-            StageTimer t(stream, MI_STAGE_EMIT);
-            const size_t emit_lds = bin_lds + 8 * 1024 * sizeof(uint32_t);
-            for (uint32_t b = 0; full && b < nbands; b++) {
-                const uint32_t by0 = b * band_rows, by1 = std::min(vp.grid_y, by0 + band_rows);
-                if (nocull)
-                    hipLaunchKernelGGL(bin_ranks_kernel<true>, dim3(nwg), dim3(BIN_THREADS), emit_lds, stream, P, geom.index_rec, geom.depth_key,
-                                       img.tile_count, img.ranges, bin.entries, vp.grid_x, vp.grid_y, by0, by1);
-                else if (full)
-                    hipLaunchKernelGGL(bin_ranks_kernel<false>, dim3(nwg), dim3(BIN_THREADS), emit_lds, stream, P, geom.index_rec, geom.depth_key,
-                                       img.tile_count, img.ranges, bin.entries, vp.grid_x, vp.grid_y, by0, by1);
-            }
-            if (!full)
-                hipLaunchKernelGGL(bin_spans_kernel<true>, dim3(nwg), dim3(1024), span_lds_bytes((size_t)lean_band_h * vp.grid_x), stream, P,
-                                   geom.index_rec, geom.depth_key, geom.band_bits, img.tile_count, img.tile_cursor, img.ranges, bin.entries, vp.grid_x, vp.grid_y,
-                                   lean_band_h, lean_nbands, (const int*)img.num_rendered, (int*)nullptr);
-        }
-        STAGE_CHECK("emit entries");
-        if (verify) {   // debugging aid: synchronous
-            uint32_t* ctr = reinterpret_cast<uint32_t*>(img.num_rendered + R_SLOTS * R_SLOT_STRIDE + NR_VERIFY);
-            HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(uint32_t), stream));
-            hipLaunchKernelGGL(verify_entries_kernel, dim3(ntiles), dim3(256), 0, stream, (uint32_t)ntiles, img.ranges, bin.entries, ctr);
-            uint32_t unwritten = 0;
-            HIP_TRY(hipMemcpyAsync(&unwritten, ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (unwritten)
-                return fail(MI_RAST_ERR_HIP, "internal error: " + std::to_string(unwritten) + " list slots were counted but not emitted "
-                                             "(count / emit passes of bin_spans_kernel disagree)");
-        }
-        const int* key_bits = img.num_rendered + R_SLOTS * R_SLOT_STRIDE + NR_KEY_BITS;
-        {
-            StageTimer t(stream, MI_STAGE_TILE_SORT);
-            // lists of up to 4096 entries: one wave per tile (bitonic network in registers, three length classes); longer ones: two classes of the LDS radix
-            // sort (1024 threads + 112 KB, 1024 threads + 144 KB / HBM ping-pong), launched only if some tile needs them.  The longest
-            // list was copied to the host right after the range scan, which finished before the emit pass above even started: this
-            // wait does not stall the queue.
-#define LAUNCH_TILE_SORT(LO, CAP, FB, NT)                                                                                 \
-    hipLaunchKernelGGL((tile_sort_kernel<LO, CAP, FB, NT>), dim3(ntiles), dim3(NT), 0, stream, (uint32_t)ntiles, img.ranges,  \
-                       bin.entries, bin.scratch, key_bits, bin.blend_list)
-            hipLaunchKernelGGL(tile_sort_wave_kernel<0>, dim3((ntiles + 3) / 4), dim3(256), 0, stream, (uint32_t)ntiles, img.ranges,
-                               (const uint2*)bin.entries, bin.blend_list);
-            HIP_TRY(hipEventSynchronize(g_host_sync.ev2));
-            img.longest_run = longest_of(g_host_sync.pinned + R_SLOTS * R_SLOT_STRIDE + NR_RUN_BOUNDS, (uint32_t)ntiles);
-            g_last_longest_run[dev] = (int)img.longest_run;
-            // lean lists: the counts are the lists' exact lengths (bin_spans_kernel), their sum a lower bound of R
-            if (full ? g_host_sync.pinned[R_SLOTS * R_SLOT_STRIDE + NR_TOTAL] != R : g_host_sync.pinned[R_SLOTS * R_SLOT_STRIDE + NR_TOTAL] > R)
-                return fail(MI_RAST_ERR_HIP, "internal error: tile counts do not add up to num_rendered");
-            const int max_tile_count = g_host_sync.pinned[R_SLOTS * R_SLOT_STRIDE + NR_LONGEST];
-            if (max_tile_count > 1024)
-                hipLaunchKernelGGL(tile_sort_wave_kernel<1>, dim3((ntiles + 3) / 4), dim3(256), 0, stream, (uint32_t)ntiles, img.ranges,
-                                   (const uint2*)bin.entries, bin.blend_list);
-            if (max_tile_count > 2048)
-                hipLaunchKernelGGL(tile_sort_wave_kernel<2>, dim3((ntiles + 3) / 4), dim3(256), 0, stream, (uint32_t)ntiles, img.ranges,
-                                   (const uint2*)bin.entries, bin.blend_list);
-            if (max_tile_count > TILE_SORT_WAVE_MAX) LAUNCH_TILE_SORT(TILE_SORT_WAVE_MAX, 6144, false, 1024);
-            if (max_tile_count > 6144) LAUNCH_TILE_SORT(6144, 8192, true, 1024);
-#undef LAUNCH_TILE_SORT
-        }
-        STAGE_CHECK("tile sort");
-    } else {
-        // no overlap at all (every tile's range is {0, 0}: the blend kernels read no list).  The range scan stores {total, longest list} into this thread's pinned words: never return while that store can still
-        // land (the next forward of this thread, on another stream, would read them)
-        HIP_TRY(hipEventSynchronize(g_host_sync.ev2));
-        img.longest_run = longest_of(g_host_sync.pinned + R_SLOTS * R_SLOT_STRIDE + NR_RUN_BOUNDS, (uint32_t)ntiles);
-        g_last_longest_run[dev] = (int)img.longest_run;
+int preprocess_stage(const Call& c, const FrontArgs& a, const BinPlan& bp)
+{
+    const int P = c.P, ntiles = (int)c.ntiles();
+    if (a.prefiltered) HIP_TRY(hipMemsetAsync(c.geom.cull_counter, 0, sizeof(int), c.stream));
+    {
+        StageTimer t(c.stream, MI_STAGE_PREPROCESS);
+        HIP_TRY(hipMemsetAsync(c.img.num_rendered, 0, R_SLOTS * R_SLOT_STRIDE * sizeof(int), c.stream));
+        // (the per-tile entry totals are zeroed by the preprocess kernel's first threads; fewer Gaussians than tiles: by a fill)
+        if (P < ntiles) HIP_TRY(hipMemsetAsync(c.img.tile_cursor, 0, (size_t)ntiles * sizeof(uint32_t), c.stream));
+        // SH colours: the workgroup's coefficient rows are staged in LDS (geometry.h), 256 rows of 3 M + 4 floats
+        const size_t sh_lds = a.colors_given ? 0 : (size_t)256 * (3 * (size_t)a.M + 4) * sizeof(float);
+        if (sh_lds > 64 * 1024) return fail(MI_RAST_ERR_INVALID, "too many SH coefficients per Gaussian (at most 16: degree 3)");
+        hipLaunchKernelGGL(preprocess_fwd_kernel, dim3((P + 255) / 256), dim3(256), sh_lds, c.stream, P, a.D, a.M, a.means3D, a.scales,
+                           a.rotations, a.opacities, a.shs, c.geom.clamped, a.cov3D_precomp, a.colors_given, c.vp, a.radii,
+                           c.geom.means2D, c.geom.depths, c.geom.cov3D, c.geom.rgb, c.geom.conic_opacity, c.geom.tiles_touched,
+                           c.geom.depth_key, c.geom.index_rec, c.img.num_rendered, a.prefiltered, c.geom.cull_counter, c.geom.band_bits,
+                           bp.lean_band_h, bp.lean_nbands, c.img.tile_cursor, (uint32_t)ntiles);
+    }
+    STAGE_CHECK(c, "preprocess");
+    if (a.prefiltered) {
+        int culled = 0;
+        HIP_TRY(hipMemcpyAsync(&culled, c.geom.cull_counter, sizeof(int), hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        if (culled)
+            return fail(MI_RAST_ERR_INVALID, "Point is filtered although prefiltered is set. This shouldn't happen!");
     }
     return MI_RAST_OK;
 }
 
-// xexp: the device library's expf (default); false under MI_RAST_FAST_EXP (include/mi_rast.h, common.h gauss_exp)
+// One-time opt-in to > 64 KB of dynamic LDS (gfx950: 160 KB per workgroup), per device.
+std::atomic<bool> g_attr_set[MAX_DEVICES];
+std::mutex g_attr_mutex;
+int opt_in_to_large_lds(int dev)
+{
+    if (g_attr_set[dev].load(std::memory_order_acquire)) return MI_RAST_OK;
+    std::lock_guard<std::mutex> lock(g_attr_mutex);
+    if (g_attr_set[dev].load(std::memory_order_relaxed)) return MI_RAST_OK;
+    const int max_lds = (int)((BIN_MAX_TILES + 11 * 1024 + 16) * sizeof(uint32_t));
+    HIP_TRY(hipFuncSetAttribute((const void*)bin_ranks_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    HIP_TRY(hipFuncSetAttribute((const void*)bin_ranks_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    HIP_TRY(hipFuncSetAttribute((const void*)bin_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
+    // (160 KB per workgroup less the kernels' static words: the band plan)
+    HIP_TRY(hipFuncSetAttribute((const void*)bin_spans_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    HIP_TRY(hipFuncSetAttribute((const void*)bin_spans_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
+    HIP_TRY(hipFuncSetAttribute((const void*)tile_ranges_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (BIN_MAX_TILES_TOTAL + 1) * (int)sizeof(uint32_t)));
+    g_attr_set[dev].store(true, std::memory_order_release);
+    return MI_RAST_OK;
+}
+
+// count pass over slices, scan over (tile, slice), scan over tiles -> ranges (binning.h).  R is known after the preprocess pass; the
+// count pass stores its partial sums into the host's pinned buffer (event ev), and the host reads them while the scans run.
+int count_and_scan_stage(const Call& c, const BinPlan& bp, const HostSync& hs)
+{
+    const int P = c.P, ntiles = (int)c.ntiles();
+    {
+        StageTimer t(c.stream, MI_STAGE_TILE_SCAN);
+        if (bp.full) {
+            const size_t cnt_lds = (size_t)(bp.band_rows + 1) * count_grid_stride(c.vp.grid_x) * sizeof(int);
+            for (uint32_t b = 0; b < bp.nbands; b++) {
+                const uint32_t by0 = b * bp.band_rows, by1 = std::min(c.vp.grid_y, by0 + bp.band_rows);
+                hipLaunchKernelGGL(bin_count_kernel, dim3(bp.nwg), dim3(BIN_THREADS), cnt_lds, c.stream, P, c.geom.index_rec, c.geom.depth_key,
+                                   c.img.tile_count, c.vp.grid_x, c.vp.grid_y, by0, by1, (const int*)c.img.num_rendered,
+                                   b == 0 ? hs.pinned_dev : (int*)nullptr);
+            }
+        } else {
+            hipLaunchKernelGGL(bin_spans_kernel<false>, dim3(bp.nwg), dim3(1024),
+                               span_lds_bytes((size_t)bp.lean_band_h * count_grid_stride(c.vp.grid_x)), c.stream, P, c.geom.index_rec,
+                               c.geom.depth_key, c.geom.band_bits, c.img.tile_count, c.img.tile_cursor, (const uint2*)nullptr, (uint2*)nullptr,
+                               c.vp.grid_x, c.vp.grid_y, bp.lean_band_h, bp.lean_nbands, (const int*)c.img.num_rendered, hs.pinned_dev);
+        }
+        HIP_TRY(hipEventRecord(hs.ev, c.stream));
+        // (one launch for both scans -- every workgroup scans its tiles over the slices, the last one to finish scans the totals
+        // behind a device-scope counter and agent-scope fences -- was built and measured in round 4: tile scan 0.058 -> 0.060 ms
+        // on cfg3; the fences and the serial tail inside the kernel cost more than the launch they save)
+        // full lists: scan over (tile, slice); lean lists: the count pass left the tile totals and every workgroup's offset itself
+        if (bp.full)
+            hipLaunchKernelGGL(scan_partials_kernel, dim3((ntiles + 63) / 64), dim3(1024), 0, c.stream, ntiles, bp.nwg,
+                               c.img.tile_count, c.img.tile_cursor);
+        const uint32_t run_cap = !(c.flags & MI_RAST_EQUAL_RUNS) ? (uint32_t)RUN_MODEL_CAP : 0u;
+        hipLaunchKernelGGL(tile_ranges_kernel, dim3(1), dim3(1024),
+                           ((size_t)std::min(ntiles, BIN_MAX_TILES_TOTAL) + 1) * sizeof(uint32_t), c.stream, ntiles, c.img.tile_cursor,
+                           c.img.ranges, c.img.words(), (const int*)c.img.num_rendered, hs.words_dev(), c.img.tile_consumed, c.img.tile_nsurv,
+                           c.img.run_bounds, run_cap, (uint32_t)RUN_MODEL_FIX);
+    }
+    STAGE_CHECK(c, "tile scan");
+    return MI_RAST_OK;
+}
+
+// The emit pass: every overlap into its tile's bucket of bin.entries, unsorted (binning.h)
+int emit_stage(const Call& c, const BinPlan& bp, int R)
+{
+    const int P = c.P, ntiles = (int)c.ntiles();
+    const bool verify = !bp.full && (c.flags & MI_RAST_VERIFY_LISTS) != 0;
+    if (verify) HIP_TRY(hipMemsetAsync(c.bin.entries, 0, (size_t)R * sizeof(uint2), c.stream));
+    {
+        StageTimer t(c.stream, MI_STAGE_EMIT);
+        if (bp.full) {
+            const size_t band_tiles = (size_t)bp.band_rows * c.vp.grid_x;
+            const size_t emit_lds = ((size_t)((band_tiles + 3) & ~(size_t)3) + 11 * 1024 + 16) * sizeof(uint32_t);
+            for (uint32_t b = 0; b < bp.nbands; b++) {
+                const uint32_t by0 = b * bp.band_rows, by1 = std::min(c.vp.grid_y, by0 + bp.band_rows);
+                with_bool(bp.nocull, [&](auto nocull) {
+                    hipLaunchKernelGGL(bin_ranks_kernel<decltype(nocull)::value>, dim3(bp.nwg), dim3(BIN_THREADS), emit_lds, c.stream, P, c.geom.index_rec,
+                                       c.geom.depth_key, c.img.tile_count, c.img.ranges, c.bin.entries, c.vp.grid_x, c.vp.grid_y, by0, by1);
+                });
+            }
+        } else {
+            hipLaunchKernelGGL(bin_spans_kernel<true>, dim3(bp.nwg), dim3(1024), span_lds_bytes((size_t)bp.lean_band_h * c.vp.grid_x), c.stream,
+                               P, c.geom.index_rec, c.geom.depth_key, c.geom.band_bits, c.img.tile_count, c.img.tile_cursor, c.img.ranges, c.bin.entries,
+                               c.vp.grid_x, c.vp.grid_y, bp.lean_band_h, bp.lean_nbands, (const int*)c.img.num_rendered, (int*)nullptr);
+        }
+    }
+    STAGE_CHECK(c, "emit entries");
+    if (verify) {   // debugging aid: synchronous
+        uint32_t* ctr = reinterpret_cast<uint32_t*>(c.img.words() + NR_VERIFY);
+        HIP_TRY(hipMemsetAsync(ctr, 0, sizeof(uint32_t), c.stream));
+        hipLaunchKernelGGL(verify_entries_kernel, dim3(ntiles), dim3(256), 0, c.stream, (uint32_t)ntiles, c.img.ranges, c.bin.entries, ctr);
+        uint32_t unwritten = 0;
+        HIP_TRY(hipMemcpyAsync(&unwritten, ctr, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        if (unwritten)
+            return fail(MI_RAST_ERR_HIP, "internal error: " + std::to_string(unwritten) + " list slots were counted but not emitted "
+                                         "(count / emit passes of bin_spans_kernel disagree)");
+    }
+    return MI_RAST_OK;
+}
+
+// The range scan stores {total, longest list, ..., run boundaries} into this thread's pinned words (event ev2): no forward returns
+// while that store can still land (the next forward of this thread, on another stream, would read them).
+int take_longest_run(Call& c, const HostSync& hs, int dev)
+{
+    HIP_TRY(hipEventSynchronize(hs.ev2));
+    c.longest_run = longest_of(hs.words() + NR_RUN_BOUNDS, c.ntiles());
+    g_last_longest_run[dev] = (int)c.longest_run;
+    return MI_RAST_OK;
+}
+
+template <int CLASS>
+void launch_tile_sort_wave(const Call& c)
+{
+    hipLaunchKernelGGL(tile_sort_wave_kernel<CLASS>, dim3((c.ntiles() + 3) / 4), dim3(256), 0, c.stream, c.ntiles(), c.img.ranges,
+                       (const uint2*)c.bin.entries, c.bin.blend_list);
+}
+template <int LO, int CAP, bool FB, int NT>
+void launch_tile_sort(const Call& c)
+{
+    hipLaunchKernelGGL((tile_sort_kernel<LO, CAP, FB, NT>), dim3(c.ntiles()), dim3(NT), 0, c.stream, c.ntiles(), c.img.ranges, c.bin.entries,
+                       c.bin.scratch, (const int*)(c.img.words() + NR_KEY_BITS), c.bin.blend_list);
+}
+
+// lists of up to 4096 entries: one wave per tile (bitonic network in registers, three length classes); longer ones: two classes of the LDS radix
+// sort (1024 threads + 112 KB, 1024 threads + 144 KB / HBM ping-pong), launched only if some tile needs them.  The longest
+// list was copied to the host right after the range scan, which finished before the emit pass even started: this
+// wait does not stall the queue.
+int sort_stage(Call& c, const BinPlan& bp, const HostSync& hs, int dev, int R)
+{
+    {
+        StageTimer t(c.stream, MI_STAGE_TILE_SORT);
+        launch_tile_sort_wave<0>(c);
+        if (int rc = take_longest_run(c, hs, dev)) return rc;
+        // lean lists: the counts are the lists' exact lengths (bin_spans_kernel), their sum a lower bound of R
+        if (bp.full ? hs.words()[NR_TOTAL] != R : hs.words()[NR_TOTAL] > R)
+            return fail(MI_RAST_ERR_HIP, "internal error: tile counts do not add up to num_rendered");
+        const int max_tile_count = hs.words()[NR_LONGEST];
+        if (max_tile_count > 1024) launch_tile_sort_wave<1>(c);
+        if (max_tile_count > 2048) launch_tile_sort_wave<2>(c);
+        if (max_tile_count > TILE_SORT_WAVE_MAX) launch_tile_sort<TILE_SORT_WAVE_MAX, 6144, false, 1024>(c);
+        if (max_tile_count > 6144) launch_tile_sort<6144, 8192, true, 1024>(c);
+    }
+    STAGE_CHECK(c, "tile sort");
+    return MI_RAST_OK;
+}
+
+// Stages shared by forward and mask_forward: CF/cuda_rasterizer/rasterizer_impl.cu:246-317.
+int geometry_and_binning(Call& c, const FrontArgs& a, int* num_rendered)
+{
+    const int dev = current_device();
+    if (dev < 0) return fail(MI_RAST_ERR_HIP, "hipGetDevice failed (or device ordinal >= 64)");
+    HostSync& hs = g_host_sync_tl[dev];
+    BinPlan bp;
+    if (int rc = plan_binning(c, bp)) return rc;
+    size_t goff[MI_GEOM_NFIELDS], ioff[MI_IMG_NFIELDS], boff[MI_BIN_NFIELDS];
+    char* geom_base = a.geometry_buffer(mi_rast_geometry_layout(c.P, goff), a.geometry_user);
+    if (!geom_base) return fail(MI_RAST_ERR_ALLOC, "geometry buffer callback returned NULL");
+    c.geom = geom_from(geom_base, c.P);
+    char* img_base = a.image_buffer(mi_rast_image_layout(c.vp.W, c.vp.H, ioff), a.image_user);
+    if (!img_base) return fail(MI_RAST_ERR_ALLOC, "image buffer callback returned NULL");
+    c.img = img_from(img_base, c.vp.W, c.vp.H);
+
+    if (int rc = preprocess_stage(c, a, bp)) return rc;
+    if (int rc = opt_in_to_large_lds(dev)) return rc;
+    if (!hs.init()) return fail(MI_RAST_ERR_HIP, "cannot allocate pinned host buffer / event");
+    if (int rc = count_and_scan_stage(c, bp, hs)) return rc;
+    HIP_TRY(hipEventRecord(hs.ev2, c.stream));
+    // rasterizer_impl.cu:280-281: the host needs num_rendered to size the binning buffer.  We wait only for
+    // the copy (event), not for the work queued behind it.
+    HIP_TRY(hipEventSynchronize(hs.ev));
+    long long Rsum = 0;
+    for (int k = 0; k < R_SLOTS; k++) Rsum += hs.pinned[k * R_SLOT_STRIDE];
+    if (Rsum > 0x7fffffffll) return fail(MI_RAST_ERR_INVALID, "more than 2^31 tile overlaps");
+    const int R = (int)Rsum;
+    *num_rendered = R;
+
+    char* bin_base = a.binning_buffer(mi_rast_binning_layout(R, boff), a.binning_user);
+    if (!bin_base) return fail(MI_RAST_ERR_ALLOC, "binning buffer callback returned NULL");
+    c.bin = bin_from(bin_base, R);
+    // no overlap at all: every tile's range is {0, 0}, and the blend kernels read no list
+    if (R == 0) return take_longest_run(c, hs, dev);
+    if (int rc = emit_stage(c, bp, R)) return rc;
+    return sort_stage(c, bp, hs, dev, R);
+}
+
+// What a forward blends (features: `channels` per Gaussian; mask: the DEPTH variant's) and a backward blend pass reads and writes
+struct FwdArgs { int channels; const float *features, *mask, *bg; float *out_color, *out_mask, *out_depth; };
+struct BwdArgs { int channels; const float *bg, *colors, *dL_dpix, *dL_dout_mask; float* dL_dcolor; };
+
+// The tile-batched kernel (blend_fwd.h): the mask-only forward; in the profiling build also a comparison kernel.  b: {0, C, C}, or one
+// 64 / 32 / 16-channel block of a wider feature, of the last one possibly only b.real channels (blend_fwd.h PARTIAL)
 template <int C, int EXTRA>
-void launch_blend_fwd(const ViewParams& vp, hipStream_t stream, const ImgPtrs& img, const BinPtrs& bin,
-                      const GeomPtrs& geom, const float* features, const float* mask, const float* bg,
-                      float* out_color, float* out_mask, float* out_depth, bool xexp, int cstride = C, int cr = C)
+void launch_blend_fwd(const Call& c, const FwdArgs& a, ChannelBlock b)
 {
-#define TILE_FWD_LAUNCH(XE, PART)                                                                                                     \
-    hipLaunchKernelGGL((blend_fwd_kernel<C, EXTRA, XE, PART>), dim3(vp.grid_x, vp.grid_y), dim3(256), 0, stream, img.ranges,              \
-                       bin.blend_list, geom.index_rec, vp.W, vp.H, features, mask, geom.depths, img.final_T, img.n_contrib,              \
-                       img.tile_consumed, img.tile_nsurv, bg, out_color, out_mask, out_depth, cstride, cr)
-    if constexpr (C == 16 && EXTRA == 0) {   // the remainder block of a feature: `cr` < 16 of its channels may exist (blend_fwd.h PARTIAL)
-        if (cr < C) {
-            if (xexp) TILE_FWD_LAUNCH(true, true);
-            else TILE_FWD_LAUNCH(false, true);
-            return;
-        }
-    }
-    if (xexp) TILE_FWD_LAUNCH(true, false);
-    else TILE_FWD_LAUNCH(false, false);
-#undef TILE_FWD_LAUNCH
+    constexpr bool MAY_BE_PARTIAL = C == 16 && EXTRA == 0;
+    with_bools(MAY_BE_PARTIAL && b.real < C, c.xexp(), [&](auto partial, auto xexp) {
+        if constexpr (MAY_BE_PARTIAL || !decltype(partial)::value)
+            hipLaunchKernelGGL((blend_fwd_kernel<C, EXTRA, decltype(xexp)::value, decltype(partial)::value>), dim3(c.vp.grid_x, c.vp.grid_y), dim3(256), 0,
+                               c.stream, c.img.ranges, c.bin.blend_list, c.geom.index_rec, c.vp.W, c.vp.H, a.features + b.c0, a.mask, c.geom.depths,
+                               c.img.final_T, c.img.n_contrib, c.img.tile_consumed, c.img.tile_nsurv, a.bg + b.c0,
+                               a.out_color + b.c0 * c.HW(), a.out_mask, a.out_depth, a.channels, b.real);
+    });
 }
 
-#ifdef MI_RAST_PROFILING
+// One wave per (tile, quadrant): 32 x the longest XCD run of tiles workgroups (blend_fwd_wave.h).  The first launch of a forward takes
+// the zero fill; the launches of further channel blocks fill nothing.
+uint32_t fwd_wave_grid(const Call& c) { return 32u * (c.longest_run ? c.longest_run : xcd_max_run(c.ntiles())); }
+// b: a 64- or 32-channel block; the remainder of a feature is a 32-channel block of which b.real channels exist (blend_fwd_wave.h PARTIAL)
 template <int C>
-void launch_blend_fwd_x3(const ViewParams& vp, hipStream_t stream, const ImgPtrs& img, const BinPtrs& bin, const GeomPtrs& geom,
-                         const float* features, const float* bg, float* out_color, bool xexp, int cstride)
+void launch_blend_fwd_wave(const Call& c, const FwdArgs& a, ChannelBlock b, FwdZeroFill& zfill)
 {
-#define X3_LAUNCH(XE, ST)                                                                                                           \
-    hipLaunchKernelGGL((blend_fwd_x3_kernel<C, XE, ST>), dim3(vp.grid_x, vp.grid_y), dim3(256), 0, stream, img.ranges, bin.blend_list, \
-                       geom.index_rec, vp.W, vp.H, features, img.final_T, img.n_contrib, img.tile_consumed, img.tile_nsurv, bg,         \
-                       out_color, cstride)
-    if (cstride == C) {
-        if (xexp) X3_LAUNCH(true, false);
-        else X3_LAUNCH(false, false);
-    } else {
-        if (xexp) X3_LAUNCH(true, true);
-        else X3_LAUNCH(false, true);
-    }
-#undef X3_LAUNCH
+    const FwdZeroFill zf = std::exchange(zfill, FwdZeroFill{nullptr, 0u, nullptr, 0u});
+    const bool is_partial = C == 32 && b.real < C;
+    with_bools(is_partial, is_partial || a.channels != C, [&](auto partial, auto strided) {
+        constexpr bool PARTIAL = decltype(partial)::value, STRIDED = decltype(strided)::value;
+        with_exp_mode(c.exp_mode(), [&](auto xm) {
+            if constexpr (!PARTIAL || (C == 32 && STRIDED))
+                hipLaunchKernelGGL((blend_fwd_wave_kernel<C, decltype(xm)::value, STRIDED, PARTIAL>), dim3(fwd_wave_grid(c)), dim3(64), 0,
+                                   c.stream, c.img.ranges, c.bin.blend_list, c.geom.index_rec, c.vp.W, c.vp.H, c.vp.grid_x, a.features + b.c0,
+                                   c.img.final_T, c.img.n_contrib, c.img.tile_consumed, c.img.tile_nsurv, a.bg + b.c0,
+                                   a.out_color + b.c0 * c.HW(), a.channels, zf, c.img.run_bounds, b.real);
+        });
+    });
 }
-#endif
-
-// One wave per (tile, quadrant): 32 x the longest XCD run of tiles workgroups (blend_fwd_wave.h).
-// xm: common.h ExpMode -- EXP_HYBRID unless the caller's flags say otherwise (exp_mode_of)
-template <int C>
-void launch_blend_fwd_wave(const ViewParams& vp, hipStream_t stream, const ImgPtrs& img, const BinPtrs& bin, const GeomPtrs& geom,
-                           const float* features, const float* bg, float* out_color, int xm, int cstride, FwdZeroFill& zfill, int cr = C)
-{
-    const uint32_t nt = vp.grid_x * vp.grid_y;
-    const uint32_t grid = 32u * (img.longest_run ? img.longest_run : xcd_max_run(nt));
-    const FwdZeroFill zf = zfill;
-    zfill = FwdZeroFill{nullptr, 0u, nullptr, 0u};   // taken: the launches of further channel blocks fill nothing
-#define FW_LAUNCH(XM, ST, PT)                                                                                                 \
-    hipLaunchKernelGGL((blend_fwd_wave_kernel<C, XM, ST, PT>), dim3(grid), dim3(64), 0, stream, img.ranges, bin.blend_list,       \
-                       geom.index_rec, vp.W, vp.H, vp.grid_x, features, img.final_T, img.n_contrib, img.tile_consumed,        \
-                       img.tile_nsurv, bg, out_color, cstride, zf, img.run_bounds, cr)
-#define FW_LAUNCH_ST(ST, PT)                                  \
-    do {                                                      \
-        if (xm == EXP_HYBRID) FW_LAUNCH(EXP_HYBRID, ST, PT);  \
-        else if (xm == EXP_EXACT) FW_LAUNCH(EXP_EXACT, ST, PT); \
-        else FW_LAUNCH(EXP_FAST, ST, PT);                     \
-    } while (0)
-    if constexpr (C == 32) {
-        if (cr < C) {   // the remainder block of a feature: `cr` of its 32 channels exist (blend_fwd_wave.h PARTIAL)
-            FW_LAUNCH_ST(true, true);
-            return;
-        }
-    }
-    if (cstride == C) FW_LAUNCH_ST(false, false);
-    else FW_LAUNCH_ST(true, false);
-#undef FW_LAUNCH_ST
-#undef FW_LAUNCH
-}
-
 template <int EXTRA>
-void launch_blend_fwd_wave_rgb(const ViewParams& vp, hipStream_t stream, const ImgPtrs& img, const BinPtrs& bin, const GeomPtrs& geom,
-                               const float* features, const float* mask, const float* bg, float* out_color, float* out_mask,
-                               float* out_depth, int xm, FwdZeroFill& zfill)
+void launch_blend_fwd_wave_rgb(const Call& c, const FwdArgs& a, FwdZeroFill& zfill)
 {
-    const uint32_t nt = vp.grid_x * vp.grid_y;
-    const uint32_t grid = 32u * (img.longest_run ? img.longest_run : xcd_max_run(nt));
-    const FwdZeroFill zf = zfill;
-    zfill = FwdZeroFill{nullptr, 0u, nullptr, 0u};
-#define RGB_LAUNCH(XM)                                                                                                                       \
-    hipLaunchKernelGGL((blend_fwd_wave_rgb_kernel<EXTRA, XM>), dim3(grid), dim3(64), 0, stream, img.ranges, bin.blend_list, geom.index_rec,   \
-                       vp.W, vp.H, vp.grid_x, features, mask, geom.depths, img.final_T, img.n_contrib, img.tile_consumed,                 \
-                       img.tile_nsurv, bg, out_color, out_mask, out_depth, zf, img.run_bounds)
-    if (xm == EXP_HYBRID) RGB_LAUNCH(EXP_HYBRID);
-    else if (xm == EXP_EXACT) RGB_LAUNCH(EXP_EXACT);
-    else RGB_LAUNCH(EXP_FAST);
-#undef RGB_LAUNCH
+    const FwdZeroFill zf = std::exchange(zfill, FwdZeroFill{nullptr, 0u, nullptr, 0u});
+    with_exp_mode(c.exp_mode(), [&](auto xm) {
+        hipLaunchKernelGGL((blend_fwd_wave_rgb_kernel<EXTRA, decltype(xm)::value>), dim3(fwd_wave_grid(c)), dim3(64), 0, c.stream, c.img.ranges,
+                           c.bin.blend_list, c.geom.index_rec, c.vp.W, c.vp.H, c.vp.grid_x, a.features, a.mask, c.geom.depths, c.img.final_T,
+                           c.img.n_contrib, c.img.tile_consumed, c.img.tile_nsurv, a.bg, a.out_color, a.out_mask, a.out_depth, zf,
+                           c.img.run_bounds);
+    });
 }
 
-template <int C, bool MASKGRAD>
-void launch_blend_bwd(const ViewParams& vp, hipStream_t stream, const ImgPtrs& img, const BinPtrs& bin,
-                      const GeomPtrs& geom, const float* colors, const float* bg, const float* dL_dpix,
-                      const float* dL_dout_mask, float* dL_dcolor, bool xexp)
+// One wave per (tile, quadrant), a work queue per XCD behind the static share (blend_bwd_wave.h).  CR: channels of the block that exist at
+// compile time -- 3 of 16 for RGB, C for a whole block, 0 for the partial block of a feature (then `real` of its 16 channels exist).
+// (the row stride is a compile-time constant unless the launch handles one channel block of a wider feature)
+template <int C, int CR, bool MASKGRAD>
+void launch_blend_bwd_wave(const Call& c, const BwdArgs& a, int c0, int real, uint32_t* queue_ctr)
 {
-    if (xexp)
-        hipLaunchKernelGGL((blend_bwd_kernel<C, MASKGRAD, true>), dim3(vp.grid_x, vp.grid_y), dim3(256), 0, stream, img.ranges,
-                           bin.blend_list, geom.index_rec, img.tile_nsurv, vp.W, vp.H, bg, colors, img.final_T, img.n_contrib, dL_dpix,
-                           dL_dout_mask, geom.bwd_pack, dL_dcolor);
-    else
-        hipLaunchKernelGGL((blend_bwd_kernel<C, MASKGRAD, false>), dim3(vp.grid_x, vp.grid_y), dim3(256), 0, stream, img.ranges,
-                           bin.blend_list, geom.index_rec, img.tile_nsurv, vp.W, vp.H, bg, colors, img.final_T, img.n_contrib, dL_dpix,
-                           dL_dout_mask, geom.bwd_pack, dL_dcolor);
+    const uint32_t nt = c.ntiles();
+    with_bools(CR == 0 || a.channels != CR, c.xexp(), [&](auto strided, auto xexp) {
+        if constexpr (CR != 0 || decltype(strided)::value)
+            hipLaunchKernelGGL((blend_bwd_wave_kernel<C, CR, MASKGRAD, decltype(xexp)::value, decltype(strided)::value>),
+                               dim3(32u * xcd_static_len_max(nt) + 4u * xcd_queued_tiles_max(nt)), dim3(64), 0, c.stream, c.img.ranges,
+                               c.bin.blend_list, c.geom.index_rec, c.img.tile_nsurv, c.vp.W, c.vp.H, c.vp.grid_x, nt, a.bg + c0, a.colors + c0,
+                               c.img.final_T, c.img.n_contrib, a.dL_dpix + c0 * c.HW(), a.dL_dout_mask, c.geom.bwd_pack, a.dL_dcolor + c0,
+                               queue_ctr, a.channels, real, c.img.run_bounds);
+    });
+}
+
+// Features-only backward, one wave per half tile (blend_bwd_feat.h): alpha, T, dF = W^T dL and the feature-row atomics of one
+// whole channel block
+template <int C>
+void launch_blend_bwd_feat(const Call& c, const BwdArgs& a, int c0, uint32_t* queue_ctr)
+{
+    const uint32_t nt = c.ntiles();
+    with_bools(a.channels != C, c.xexp(), [&](auto strided, auto xexp) {
+        hipLaunchKernelGGL((blend_bwd_feat_kernel<C, decltype(xexp)::value, decltype(strided)::value>),
+                           dim3(16u * xcd_static_len_max(nt) + 2u * xcd_queued_tiles_max(nt)), dim3(64), 0, c.stream, c.img.ranges,
+                           c.bin.blend_list, c.geom.index_rec, c.img.tile_nsurv, c.vp.W, c.vp.H, c.vp.grid_x, nt, c.img.final_T,
+                           c.img.n_contrib, a.dL_dpix + c0 * c.HW(), a.dL_dcolor + c0, queue_ctr, a.channels, c.img.run_bounds);
+    });
+}
+
+// The mask-only tile backward (blend_bwd.h)
+void launch_mask_bwd(const Call& c, const float* dL_dout_mask)
+{
+    with_bool(c.xexp(), [&](auto xexp) {
+        hipLaunchKernelGGL(mask_bwd_kernel<decltype(xexp)::value>, dim3(c.vp.grid_x, c.vp.grid_y), dim3(256), 0, c.stream, c.img.ranges, c.bin.blend_list,
+                           c.geom.index_rec, c.img.tile_nsurv, c.vp.W, c.vp.H, c.img.final_T, c.img.n_contrib, dL_dout_mask, c.geom.bwd_pack);
+    });
 }
 
 }  // namespace
+
+#ifdef MI_RAST_PROFILING
+// ---- profiling build only (libmi_rast_prof.so, seganygaussians_amd/build.py): the comparison forwards of earlier rounds, selected by
+// MI_RAST_TILE_FWD (tile-batched bf16x3 / RGB) and MI_RAST_F32_BLEND (f32 FMA chain), and the blend kernels' XCD stamps ----
+// round 2's tile-batched bf16x3 forward (blend_fwd_x3.h) over one 64- or 32-channel block
+template <int C>
+static void launch_blend_fwd_x3(const Call& c, const FwdArgs& a, ChannelBlock b)
+{
+    with_bools(a.channels != C, c.xexp(), [&](auto strided, auto xexp) {
+        hipLaunchKernelGGL((blend_fwd_x3_kernel<C, decltype(xexp)::value, decltype(strided)::value>), dim3(c.vp.grid_x, c.vp.grid_y), dim3(256), 0,
+                           c.stream, c.img.ranges, c.bin.blend_list, c.geom.index_rec, c.vp.W, c.vp.H, a.features + b.c0, c.img.final_T,
+                           c.img.n_contrib, c.img.tile_consumed, c.img.tile_nsurv, a.bg + b.c0, a.out_color + b.c0 * c.HW(), a.channels);
+    });
+}
+// Returns whether a comparison kernel blended the image (false: the flags ask for none that exists for this input, RGB with
+// MI_RAST_F32_BLEND among them: the product kernels blend).
+static bool blend_fwd_comparison(const Call& c, const FwdArgs& a)
+{
+    const bool tile_fwd = (c.flags & MI_RAST_TILE_FWD) != 0, f32_blend = (c.flags & MI_RAST_F32_BLEND) != 0;
+    if (a.mask || a.channels == 3) {
+        if (!tile_fwd) return false;
+        if (a.mask) launch_blend_fwd<3, 2>(c, a, ChannelBlock{0, 3, 3});
+        else launch_blend_fwd<3, 0>(c, a, ChannelBlock{0, 3, 3});
+        return true;
+    }
+    if (!tile_fwd && !f32_blend) return false;
+    // (the comparison kernels have no partial 32-channel form: what is left behind the last whole block takes the tile-batched
+    // 16-channel kernel, in one or two blocks)
+    for_channel_blocks(a.channels, 16, [&](ChannelBlock b) {
+        if (b.width == 16) launch_blend_fwd<16, 0>(c, a, b);
+        else if (b.width == 32) f32_blend ? launch_blend_fwd<32, 0>(c, a, b) : launch_blend_fwd_x3<32>(c, a, b);
+        else f32_blend ? launch_blend_fwd<64, 0>(c, a, b) : launch_blend_fwd_x3<64>(c, a, b);
+    });
+    return true;
+}
+
+// Profiling build only (tools/xcd_stamps.py; not part of include/mi_rast.h): from the blend kernels' per-wave stamps since the last reset,
+// per XCD x: out[x] = latest end of a wave, out[8 + x] = earliest start, out[16 + x] = waves -- ticks of the constant 100-MHz clock.
+extern "C" int mi_rast_xcd_stamps(unsigned long long* out, int reset)
+{
+    static std::vector<unsigned long long> h(2 * (size_t)MI_XCD_LOG_WAVES);
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_xcd_log), h.size() * sizeof(unsigned long long)));
+    for (int k = 0; k < 24; k++) out[k] = 0ull;
+    for (size_t b = 0; b < MI_XCD_LOG_WAVES; b++) {
+        const unsigned long long s0 = h[2 * b], e0 = h[2 * b + 1];
+        if (s0 == 0ull || e0 == 0ull) continue;
+        const int x = (int)(s0 & 7ull);
+        const unsigned long long st = s0 >> 3;
+        out[x] = std::max(out[x], e0);
+        out[8 + x] = out[8 + x] == 0ull ? st : std::min(out[8 + x], st);
+        out[16 + x]++;
+    }
+    if (reset) {
+        std::fill(h.begin(), h.end(), 0ull);
+        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_log), h.data(), h.size() * sizeof(unsigned long long)));
+    }
+    return MI_RAST_OK;
+}
+#endif
 
 extern "C" {
 
@@ -680,32 +822,6 @@ size_t mi_rast_binning_layout(int R, size_t* off)
     return c.off;
 }
 
-#ifdef MI_RAST_PROFILING
-// Profiling build only (tools/xcd_stamps.py; not part of include/mi_rast.h): from the blend kernels' per-wave stamps since the last reset,
-// per XCD x: out[x] = latest end of a wave, out[8 + x] = earliest start, out[16 + x] = waves -- ticks of the constant 100-MHz clock.
-int mi_rast_xcd_stamps(unsigned long long* out, int reset)
-{
-    static std::vector<unsigned long long> h(2 * (size_t)MI_XCD_LOG_WAVES);
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(g_xcd_log), h.size() * sizeof(unsigned long long)));
-    for (int k = 0; k < 24; k++) out[k] = 0ull;
-    for (size_t b = 0; b < MI_XCD_LOG_WAVES; b++) {
-        const unsigned long long s0 = h[2 * b], e0 = h[2 * b + 1];
-        if (s0 == 0ull || e0 == 0ull) continue;
-        const int x = (int)(s0 & 7ull);
-        const unsigned long long st = s0 >> 3;
-        out[x] = std::max(out[x], e0);
-        out[8 + x] = out[8 + x] == 0ull ? st : std::min(out[8 + x], st);
-        out[16 + x]++;
-    }
-    if (reset) {
-        std::fill(h.begin(), h.end(), 0ull);
-        HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(g_xcd_log), h.data(), h.size() * sizeof(unsigned long long)));
-    }
-    return MI_RAST_OK;
-}
-#endif
-
 int mi_rast_profile_enable(int on)
 {
     if (on && !profile_events(current_device())) return fail(MI_RAST_ERR_HIP, "hipEventCreate failed");
@@ -718,7 +834,7 @@ int mi_rast_profile_enable(int on)
 int mi_rast_profile_read(float* ms)
 {
     const int dev = current_device();
-    ProfileEvents* pe = dev >= 0 && g_prof[dev].created ? &g_prof[dev] : nullptr;
+    ProfileEvents* pe = dev >= 0 && g_prof[dev].created.load(std::memory_order_acquire) ? &g_prof[dev] : nullptr;
     for (int i = 0; i < MI_STAGE_COUNT; i++) {
         ms[i] = 0.f;
         if (pe && pe->used[i]) {
@@ -731,20 +847,18 @@ int mi_rast_profile_read(float* ms)
 }
 
 // The blend stage of a forward: CF/cuda_rasterizer/rasterizer_impl.cu:319-335 (+ the zero fills for this view's backward).  Shared by
-// mi_rast_forward and mi_rast_forward_reuse.
-static int blend_forward_stage(const ViewParams& vp, hipStream_t stream, GeomPtrs& geom, ImgPtrs& img, BinPtrs& bin, int P, int channels,
-                               int width, int height, const float* background, const float* colors_precomp, const float* mask,
-                               float* out_color, float* out_mask, float* out_depth, int debug, int flags, void* features_ready_event,
-                               float* dL_dcolor_next)
+// mi_rast_forward and mi_rast_forward_reuse.  args.features: the caller's colors_precomp, or NULL for the preprocess pass's RGB.
+static int blend_forward_stage(const Call& c, const FwdArgs& args, void* features_ready_event, float* dL_dcolor_next)
 {
-    int rc;
-    const float* feature_ptr = colors_precomp != nullptr ? colors_precomp : geom.rgb;  // rasterizer_impl.cu:321
+    FwdArgs a = args;
+    if (a.features == nullptr) a.features = c.geom.rgb;  // rasterizer_impl.cu:321
+    if (a.mask == nullptr) a.out_mask = a.out_depth = nullptr;
     if (features_ready_event != nullptr) {
         // everything above depends on the geometry only; colors_precomp may still be in the making (mi_rast.h)
-        HIP_TRY(hipStreamWaitEvent(stream, (hipEvent_t)features_ready_event, 0));
+        HIP_TRY(hipStreamWaitEvent(c.stream, (hipEvent_t)features_ready_event, 0));
     }
     {
-        StageTimer t(stream, MI_STAGE_BLEND_FWD);
+        StageTimer t(c.stream, MI_STAGE_BLEND_FWD);
         // zero-fill for the backward of this view (mi_rast.h: dL_dcolor_next, MI_RAST_PREZERO_BWD): stored by the first wave-per-quadrant
         // blend launch beside its own work (blend_fwd_wave.h); tails that are not whole 16-byte units, and everything when another
         // kernel blends, by fill commands
@@ -754,90 +868,47 @@ static int blend_forward_stage(const ViewParams& vp, hipStream_t stream, GeomPtr
             // zeros on cfg3); beyond that the zeros are HBM time wherever they are stored, and the fill engine stores them faster
             // (cfg5, 5 M x 64 channels: 1.44 GB of zeros against a 435-MB image: blend 0.38 -> 0.67 ms with the fill on board,
             // 0.22 ms as fill commands).
-            const size_t ride_limit = (size_t)channels * width * height * sizeof(float);
+            const size_t ride_limit = (size_t)a.channels * c.vp.W * c.vp.H * sizeof(float);
             size_t riding = 0;
             auto region = [&](float* ptr, size_t bytes, float4*& p, uint32_t& n16) -> int {
                 if (ptr == nullptr || bytes == 0) return MI_RAST_OK;
                 if ((reinterpret_cast<uintptr_t>(ptr) & 15u) != 0 || (bytes >> 4) > 0xFFFFFFFFull || riding + bytes > ride_limit) {
-                    HIP_TRY(hipMemsetAsync(ptr, 0, bytes, stream));
+                    HIP_TRY(hipMemsetAsync(ptr, 0, bytes, c.stream));
                     return MI_RAST_OK;
                 }
                 p = reinterpret_cast<float4*>(ptr);
                 n16 = (uint32_t)(bytes >> 4);
                 riding += bytes;
-                if (bytes & 15u) HIP_TRY(hipMemsetAsync(reinterpret_cast<char*>(ptr) + (bytes & ~(size_t)15), 0, bytes & 15u, stream));
+                if (bytes & 15u) HIP_TRY(hipMemsetAsync(reinterpret_cast<char*>(ptr) + (bytes & ~(size_t)15), 0, bytes & 15u, c.stream));
                 return MI_RAST_OK;
             };
-            if ((rc = region(dL_dcolor_next, (size_t)P * channels * sizeof(float), zfill.a, zfill.na))) return rc;
-            if (flags & MI_RAST_PREZERO_BWD)
-                if ((rc = region(geom.bwd_pack, bwd_pack_bytes(P), zfill.b, zfill.nb))) return rc;
+            if (int rc = region(dL_dcolor_next, (size_t)c.P * a.channels * sizeof(float), zfill.a, zfill.na)) return rc;
+            if (c.flags & MI_RAST_PREZERO_BWD)
+                if (int rc = region(c.geom.bwd_pack, bwd_pack_bytes(c.P), zfill.b, zfill.nb)) return rc;
         }
-        const bool xexp = (flags & MI_RAST_FAST_EXP) == 0;   // the kernels without a hybrid form: expf unless MI_RAST_FAST_EXP
-        const int xm = (flags & MI_RAST_FAST_EXP) ? EXP_FAST : (flags & MI_RAST_EXACT_EXP) ? EXP_EXACT : EXP_HYBRID;   // the wave-per-quadrant kernels
         // Product kernels: the wave-per-quadrant forward (RGB, RGB + mask + depth, 64- and 32-channel blocks; the remainder of a feature is a
-        // partial 32-channel block of the same kernel).  The comparison kernels of earlier rounds -- MI_RAST_TILE_FWD (tile-batched bf16x3 / RGB),
-        // MI_RAST_F32_BLEND (f32 FMA chain) -- exist in the profiling build only (libmi_rast_prof.so, seganygaussians_amd/build.py).
+        // partial 32-channel block of the same kernel).  The comparison kernels of earlier rounds exist in the profiling build only.
 #ifdef MI_RAST_PROFILING
-        const bool tile_fwd = (flags & MI_RAST_TILE_FWD) != 0, f32_blend = (flags & MI_RAST_F32_BLEND) != 0;
+        const bool compared = blend_fwd_comparison(c, a);
 #else
-        constexpr bool tile_fwd = false, f32_blend = false;
-        if (flags & (MI_RAST_TILE_FWD | MI_RAST_F32_BLEND))
+        const bool compared = false;
+        if (c.flags & (MI_RAST_TILE_FWD | MI_RAST_F32_BLEND))
             return fail(MI_RAST_ERR_INVALID, "MI_RAST_TILE_FWD / MI_RAST_F32_BLEND select comparison kernels of the profiling build "
                                              "(libmi_rast_prof.so: python -m seganygaussians_amd.build --profiling, MI_RAST_LIB=<path>)");
 #endif
-        if (mask || channels == 3) {
-#ifdef MI_RAST_PROFILING
-            if (tile_fwd && mask) launch_blend_fwd<3, 2>(vp, stream, img, bin, geom, feature_ptr, mask, background, out_color, out_mask, out_depth, xexp);
-            else if (tile_fwd) launch_blend_fwd<3, 0>(vp, stream, img, bin, geom, feature_ptr, nullptr, background, out_color, nullptr, nullptr, xexp);
-            else
-#endif
-            if (mask) launch_blend_fwd_wave_rgb<2>(vp, stream, img, bin, geom, feature_ptr, mask, background, out_color, out_mask, out_depth, xm, zfill);
-            else launch_blend_fwd_wave_rgb<0>(vp, stream, img, bin, geom, feature_ptr, nullptr, background, out_color, nullptr, nullptr, xm, zfill);
-        } else {
-            // feature channels in blocks of 64 / 32 (one launch per block; see channels_supported); what is left behind the last whole
-            // block -- 1 .. 31 channels -- is a PARTIAL 32-channel block of the same wave-per-quadrant kernel
-            const size_t HW = (size_t)width * height;
-            for (int c0 = 0; c0 < channels;) {
-                const int rem = channels - c0;
-                const int cb = rem >= 64 ? 64 : 32;
-                const float* f = feature_ptr + c0;
-                const float* bgp = background + c0;
-                float* out = out_color + (size_t)c0 * HW;
-                if (cb == 64) {
-#ifdef MI_RAST_PROFILING
-                    if (f32_blend) launch_blend_fwd<64, 0>(vp, stream, img, bin, geom, f, nullptr, bgp, out, nullptr, nullptr, xexp, channels);
-                    else if (tile_fwd) launch_blend_fwd_x3<64>(vp, stream, img, bin, geom, f, bgp, out, xexp, channels);
-                    else
-#endif
-                    launch_blend_fwd_wave<64>(vp, stream, img, bin, geom, f, bgp, out, xm, channels, zfill);
-                } else if (rem >= 32) {
-#ifdef MI_RAST_PROFILING
-                    if (f32_blend) launch_blend_fwd<32, 0>(vp, stream, img, bin, geom, f, nullptr, bgp, out, nullptr, nullptr, xexp, channels);
-                    else if (tile_fwd) launch_blend_fwd_x3<32>(vp, stream, img, bin, geom, f, bgp, out, xexp, channels);
-                    else
-#endif
-                    launch_blend_fwd_wave<32>(vp, stream, img, bin, geom, f, bgp, out, xm, channels, zfill);
-                } else {
-#ifdef MI_RAST_PROFILING
-                    // (the comparison kernels have no partial 32-channel form: the tile-batched 16-channel kernel, in one or two blocks)
-                    if (f32_blend || tile_fwd) {
-                        for (int c1 = 0; c1 < rem; c1 += 16)
-                            launch_blend_fwd<16, 0>(vp, stream, img, bin, geom, f + c1, nullptr, bgp + c1, out + (size_t)c1 * HW, nullptr, nullptr, xexp,
-                                                    channels, std::min(16, rem - c1));
-                    } else
-#endif
-                    launch_blend_fwd_wave<32>(vp, stream, img, bin, geom, f, bgp, out, xm, channels, zfill, rem);
-                }
-                c0 += cb;
-            }
-        }
-        (void)tile_fwd;
-        (void)f32_blend;
+        if (compared) {}   // a comparison kernel has blended
+        else if (a.mask) launch_blend_fwd_wave_rgb<2>(c, a, zfill);
+        else if (a.channels == 3) launch_blend_fwd_wave_rgb<0>(c, a, zfill);
+        else   // one launch per channel block
+            for_channel_blocks(a.channels, 32, [&](ChannelBlock b) {
+                if (b.width == 64) launch_blend_fwd_wave<64>(c, a, b, zfill);
+                else launch_blend_fwd_wave<32>(c, a, b, zfill);
+            });
         // no wave-per-quadrant launch took the fill (tile-batched / f32 / 16-channel kernels): fill commands
-        if (zfill.na) HIP_TRY(hipMemsetAsync(zfill.a, 0, (size_t)zfill.na << 4, stream));
-        if (zfill.nb) HIP_TRY(hipMemsetAsync(zfill.b, 0, (size_t)zfill.nb << 4, stream));
+        if (zfill.na) HIP_TRY(hipMemsetAsync(zfill.a, 0, (size_t)zfill.na << 4, c.stream));
+        if (zfill.nb) HIP_TRY(hipMemsetAsync(zfill.b, 0, (size_t)zfill.nb << 4, c.stream));
     }
-    STAGE_CHECK("render");
+    STAGE_CHECK(c, "render");
     return MI_RAST_OK;
 }
 
@@ -850,25 +921,17 @@ int mi_rast_forward(mi_rast_resize_fn geometry_buffer, void* geometry_user, mi_r
                     const float* mask, float* out_color, float* out_mask, float* out_depth, int* radii, int debug,
                     int flags, void* features_ready_event, float* dL_dcolor_next, void* stream_, int* num_rendered)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (num_rendered) *num_rendered = 0;
     if (int rc = check_forward_args(P, channels, width, height, colors_precomp, mask)) return rc;
     if (!num_rendered || !radii || !out_color) return fail(MI_RAST_ERR_INVALID, "null output pointer");
 
-    const ViewParams vp = make_view(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, scale_modifier, width, height);
-    int rc;
-
-    GeomPtrs geom;
-    ImgPtrs img;
-    BinPtrs bin;
-    rc = geometry_and_binning(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P,
-                              D, M, width, height, means3D, shs, colors_precomp != nullptr, opacities, scales,
-                              rotations, cov3D_precomp, vp, prefiltered, radii, debug, flags, stream, geom, img, bin,
-                              num_rendered);
-    if (rc) return rc;
-
-    return blend_forward_stage(vp, stream, geom, img, bin, P, channels, width, height, background, colors_precomp, mask, out_color, out_mask,
-                               out_depth, debug, flags, features_ready_event, dL_dcolor_next);
+    Call c{make_view(viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, scale_modifier, width, height), (hipStream_t)stream_, debug, flags, P,
+           {}, {}, {}, 0u};
+    const FrontArgs front{geometry_buffer, binning_buffer, image_buffer, geometry_user, binning_user, image_user, D, M, colors_precomp != nullptr,
+                          prefiltered, means3D, shs, opacities, scales, rotations, cov3D_precomp, radii};
+    if (int rc = geometry_and_binning(c, front, num_rendered)) return rc;
+    return blend_forward_stage(c, FwdArgs{channels, colors_precomp, mask, background, out_color, out_mask, out_depth}, features_ready_event,
+                               dL_dcolor_next);
 }
 
 // Extension (no counterpart in the reference; include/mi_rast.h): the blend stage alone over the state a previous mi_rast_forward
@@ -878,26 +941,22 @@ int mi_rast_forward_reuse(int P, int channels, int R, const float* background, i
                           int longest_run, const float* mask, float* out_color, float* out_mask, float* out_depth, int flags,
                           void* features_ready_event, float* dL_dcolor_next, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_forward_args(P, channels, width, height, colors_precomp, mask)) return rc;
     if (!geom_buffer || !binning_buffer || !cached_ranges || !cached_words || !img_buffer || !out_color) return fail(MI_RAST_ERR_INVALID, "null pointer");
-    const ViewParams vp = make_blend_view(width, height);
-    const int debug = 0;
-    GeomPtrs geom = geom_from(geom_buffer, P);
-    BinPtrs bin = bin_from(binning_buffer, R);
-    ImgPtrs img = img_from(img_buffer, width, height);
-    const uint32_t ntiles = vp.grid_x * vp.grid_y;
-    img.longest_run = longest_run > 0 ? std::min((uint32_t)longest_run, xcd_max_run(ntiles)) : 0u;
+    Call c{make_blend_view(width, height), (hipStream_t)stream_, 0, flags, P, geom_from(geom_buffer, P), img_from(img_buffer, width, height),
+           bin_from(binning_buffer, R), 0u};
+    const uint32_t ntiles = c.ntiles();
+    c.longest_run = longest_run > 0 ? std::min((uint32_t)longest_run, xcd_max_run(ntiles)) : 0u;
     {
         // the per-view words of the image buffer that the binning stages of the cached forward wrote: tile ranges, {R, longest list,
         // key bits}, the XCD run boundaries -- copied; the per-tile walk counters of the blend kernels -- zeroed (binning.h)
-        StageTimer t(stream, MI_STAGE_TILE_SCAN);
-        hipLaunchKernelGGL(reuse_image_state_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, stream, ntiles, (const uint2*)cached_ranges,
-                           cached_words, img.ranges, img.num_rendered + R_SLOTS * R_SLOT_STRIDE, img.tile_consumed, img.tile_nsurv);
+        StageTimer t(c.stream, MI_STAGE_TILE_SCAN);
+        hipLaunchKernelGGL(reuse_image_state_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, c.stream, ntiles, (const uint2*)cached_ranges,
+                           cached_words, c.img.ranges, c.img.words(), c.img.tile_consumed, c.img.tile_nsurv);
     }
-    STAGE_CHECK("reuse image state");
-    return blend_forward_stage(vp, stream, geom, img, bin, P, channels, width, height, background, colors_precomp, mask, out_color, out_mask,
-                               out_depth, debug, flags, features_ready_event, dL_dcolor_next);
+    STAGE_CHECK(c, "reuse image state");
+    return blend_forward_stage(c, FwdArgs{channels, colors_precomp, mask, background, out_color, out_mask, out_depth}, features_ready_event,
+                               dL_dcolor_next);
 }
 
 // Content fingerprints of up to MI_FP_MAX device arrays (a 64-bit sum of position-dependent word hashes each): what a caller keys
@@ -948,9 +1007,7 @@ int mi_rast_backward(int P, int D, int M, int channels, int R, const float* back
                      float* dL_dopacity, float* dL_dcolor, float* dL_dmask, float* dL_dmean3D, float* dL_dcov3D,
                      float* dL_dsh, float* dL_dscale, float* dL_drot, int debug, int flags, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0) return MI_RAST_OK;
-    const bool xexp = (flags & MI_RAST_FAST_EXP) == 0;
     if (!channels_supported(channels)) return fail(MI_RAST_ERR_INVALID, "unsupported channel count (supported: 1 .. 256)");
     const bool maskgrad = dL_dmask != nullptr;
     if (maskgrad && (channels != 3 || !dL_dout_mask)) return fail(MI_RAST_ERR_INVALID, "mask gradient needs 3 channels and dL_dout_mask");
@@ -959,103 +1016,53 @@ int mi_rast_backward(int P, int D, int M, int channels, int R, const float* back
     if (feat_only && (!mi_rast_features_only_supported(channels) || colors_precomp == nullptr || maskgrad || dL_dcolor == nullptr))
         return fail(MI_RAST_ERR_INVALID, "MI_RAST_BWD_FEATURES_ONLY needs colors_precomp, dL_dcolor and a channel count that is a multiple of 16");
 
-    const ViewParams vp = make_view(viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier, width, height);
-
-    const GeomPtrs geom = geom_from(geom_buffer, P);
-    const BinPtrs bin = bin_from(binning_buffer, R);
-    const ImgPtrs img = img_from(img_buffer, width, height);
-    const float* color_ptr = (colors_precomp != nullptr) ? colors_precomp : geom.rgb;  // rasterizer_impl.cu:389
+    const Call c{make_view(viewmatrix, projmatrix, campos, tan_fovx, tan_fovy, scale_modifier, width, height), (hipStream_t)stream_, debug, flags, P,
+                 geom_from(geom_buffer, P), img_from(img_buffer, width, height), bin_from(binning_buffer, R), 0u};
+    const GeomPtrs& geom = c.geom;
+    const BwdArgs a{channels, background, colors_precomp != nullptr ? colors_precomp : geom.rgb /* rasterizer_impl.cu:389 */, dL_dpix,
+                    dL_dout_mask, dL_dcolor};
     {
-        StageTimer t(stream, MI_STAGE_BLEND_BWD);
+        StageTimer t(c.stream, MI_STAGE_BLEND_BWD);
+        // behind the packed field gradients: the work-queue counters, one set of eight per channel block
+        const size_t fields_bytes = (size_t)P * 8 * sizeof(float);
+        uint32_t* queue_ctr = reinterpret_cast<uint32_t*>(geom.bwd_pack + (size_t)P * 8);
         // (MI_RAST_PREZERO_BWD: the forward of this view left the block zeroed, and no backward has run on it since)
-        // (features only: the packed fields are not used, the work-queue counters behind them are)
-        if (!(flags & MI_RAST_PREZERO_BWD))
-            HIP_TRY(hipMemsetAsync(feat_only ? (void*)(geom.bwd_pack + (size_t)P * 8) : (void*)geom.bwd_pack, 0,
-                                   bwd_pack_bytes(P) - (feat_only ? (size_t)P * 8 * sizeof(float) : 0), stream));
-        uint32_t* queue_ctr = reinterpret_cast<uint32_t*>(geom.bwd_pack + (size_t)P * 8);   // one set of eight counters per channel block
-        const float* bg_blk = background;
-        const float* colors_blk = color_ptr;
-        const float* dpix_blk = dL_dpix;
-        float* dcolor_blk = dL_dcolor;
-        int cstride = channels;
-        int cr_blk = 0;   // channels of a partial block that exist (blend_bwd_wave.h: CR == 0)
-        const uint32_t nt_ = vp.grid_x * vp.grid_y;
-#define LAUNCH_BWD_WAVE_(XE, ST, ...)                                                                                         \
-    hipLaunchKernelGGL((blend_bwd_wave_kernel<__VA_ARGS__, XE, ST>), dim3(32u * xcd_static_len_max(nt_) + 4u * xcd_queued_tiles_max(nt_)), dim3(64), 0,    \
-                       stream, img.ranges, bin.blend_list, geom.index_rec, img.tile_nsurv, vp.W, vp.H, vp.grid_x, nt_, bg_blk, colors_blk, \
-                       img.final_T, img.n_contrib, dpix_blk, dL_dout_mask, geom.bwd_pack, dcolor_blk, queue_ctr, cstride, cr_blk, img.run_bounds)
-#define LAUNCH_BWD_WAVE_ST(ST, ...)                                                 \
-    do {                                                                            \
-        if (xexp) LAUNCH_BWD_WAVE_(true, ST, __VA_ARGS__);                          \
-        else LAUNCH_BWD_WAVE_(false, ST, __VA_ARGS__);                              \
-    } while (0)
-// (the row stride is a compile-time constant unless the launch handles one channel block of a wider feature)
-#define LAUNCH_BWD_WAVE(C_, CR_, MG_)                                               \
-    do {                                                                            \
-        if (cstride == CR_) LAUNCH_BWD_WAVE_ST(false, C_, CR_, MG_);                \
-        else LAUNCH_BWD_WAVE_ST(true, C_, CR_, MG_);                                \
-    } while (0)
-        if (feat_only) {
-            // one launch per channel block of 64 / 32 / 16 channels (blend_bwd_feat.h: one wave per half tile): alpha, T, dF = W^T dL and
-            // the feature-row atomics
-#define LAUNCH_BWD_HALF_(C_, XE, ST)                                                                                             \
-    hipLaunchKernelGGL((blend_bwd_feat_kernel<C_, XE, ST>), dim3(16u * xcd_static_len_max(nt_) + 2u * xcd_queued_tiles_max(nt_)), dim3(64), 0,  \
-                       stream, img.ranges, bin.blend_list, geom.index_rec, img.tile_nsurv, vp.W, vp.H, vp.grid_x, nt_, img.final_T,             \
-                       img.n_contrib, dpix_blk, dcolor_blk, queue_ctr, cstride, img.run_bounds)
-#define LAUNCH_BWD_HALF(C_)                                                                  \
-    do {                                                                                     \
-        if (cstride == C_) { if (xexp) LAUNCH_BWD_HALF_(C_, true, false); else LAUNCH_BWD_HALF_(C_, false, false); } \
-        else { if (xexp) LAUNCH_BWD_HALF_(C_, true, true); else LAUNCH_BWD_HALF_(C_, false, true); }                 \
-    } while (0)
-            const size_t HW = (size_t)width * height;
-            for (int c0 = 0; c0 < channels;) {
-                const int cb = channel_block(channels - c0);
-                dpix_blk = dL_dpix + (size_t)c0 * HW;
-                dcolor_blk = dL_dcolor + c0;
-                if (cb == 64) LAUNCH_BWD_HALF(64);
-                else if (cb == 32) LAUNCH_BWD_HALF(32);
-                else LAUNCH_BWD_HALF(16);
+        // (features only: the packed fields are not used, the counters behind them are)
+        if (!(flags & MI_RAST_PREZERO_BWD)) {
+            if (feat_only) HIP_TRY(hipMemsetAsync(queue_ctr, 0, bwd_pack_bytes(P) - fields_bytes, c.stream));
+            else HIP_TRY(hipMemsetAsync(geom.bwd_pack, 0, bwd_pack_bytes(P), c.stream));
+        }
+        if (feat_only)
+            for_channel_blocks(channels, 16, [&](ChannelBlock b) {
+                if (b.width == 64) launch_blend_bwd_feat<64>(c, a, b.c0, queue_ctr);
+                else if (b.width == 32) launch_blend_bwd_feat<32>(c, a, b.c0, queue_ctr);
+                else launch_blend_bwd_feat<16>(c, a, b.c0, queue_ctr);
                 queue_ctr += 8 * XCD_QUEUE_STRIDE;
-                c0 += cb;
-            }
-#undef LAUNCH_BWD_HALF
-#undef LAUNCH_BWD_HALF_
-        } else if (maskgrad) LAUNCH_BWD_WAVE(16, 3, true);
-        else if (channels == 3) LAUNCH_BWD_WAVE(16, 3, false);
-        else {
+            });
+        else if (maskgrad) launch_blend_bwd_wave<16, 3, true>(c, a, 0, 0, queue_ctr);   // RGB, 3 of a 16-channel block, + the DEPTH variant's dL_dmask
+        else if (channels == 3) launch_blend_bwd_wave<16, 3, false>(c, a, 0, 0, queue_ctr);
+        else
             // one launch per channel block: the feature gradient of the block, and the block's share of the geometry gradients
             // (dL/dalpha is a sum over channels), which the launches accumulate in the packed record
-            const size_t HW = (size_t)width * height;
-            for (int c0 = 0; c0 < channels;) {
-                const int cb = channel_block(channels - c0);
-                bg_blk = background + c0;
-                colors_blk = color_ptr + c0;
-                dpix_blk = dL_dpix + (size_t)c0 * HW;
-                dcolor_blk = dL_dcolor + c0;
-                cr_blk = std::min(cb, channels - c0);
-                if (cb == 64) LAUNCH_BWD_WAVE(64, 64, false);
-                else if (cb == 32) LAUNCH_BWD_WAVE(32, 32, false);
-                else if (cr_blk == 16) LAUNCH_BWD_WAVE(16, 16, false);
-                else LAUNCH_BWD_WAVE_ST(true, 16, 0, false);   // partial block: cr_blk of its 16 channels exist
+            for_channel_blocks(channels, 16, [&](ChannelBlock b) {
+                if (b.width == 64) launch_blend_bwd_wave<64, 64, false>(c, a, b.c0, b.real, queue_ctr);
+                else if (b.width == 32) launch_blend_bwd_wave<32, 32, false>(c, a, b.c0, b.real, queue_ctr);
+                else if (b.real == 16) launch_blend_bwd_wave<16, 16, false>(c, a, b.c0, b.real, queue_ctr);
+                else launch_blend_bwd_wave<16, 0, false>(c, a, b.c0, b.real, queue_ctr);   // partial block: b.real of its 16 channels exist
                 queue_ctr += 8 * XCD_QUEUE_STRIDE;
-                c0 += cb;
-            }
-        }
-#undef LAUNCH_BWD_WAVE
-#undef LAUNCH_BWD_WAVE_ST
-#undef LAUNCH_BWD_WAVE_
+            });
     }
-    STAGE_CHECK("render backward");
+    STAGE_CHECK(c, "render backward");
 
     if (feat_only) return MI_RAST_OK;
     const float* cov3D_ptr = (cov3D_precomp != nullptr) ? cov3D_precomp : geom.cov3D;  // rasterizer_impl.cu:411
     {
-        StageTimer t(stream, MI_STAGE_GEOM_BWD);
-        hipLaunchKernelGGL(geometry_bwd_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, D, M, means3D, radii, shs,
-                           geom.clamped, scales, rotations, cov3D_ptr, vp, geom.bwd_pack, dL_dmean2D, dL_dconic, dL_dopacity,
+        StageTimer t(c.stream, MI_STAGE_GEOM_BWD);
+        hipLaunchKernelGGL(geometry_bwd_kernel, dim3((P + 255) / 256), dim3(256), 0, c.stream, P, D, M, means3D, radii, shs,
+                           geom.clamped, scales, rotations, cov3D_ptr, c.vp, geom.bwd_pack, dL_dmean2D, dL_dconic, dL_dopacity,
                            dL_dmask, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
     }
-    STAGE_CHECK("preprocess backward");
+    STAGE_CHECK(c, "preprocess backward");
     return MI_RAST_OK;
 }
 
@@ -1078,44 +1085,36 @@ int mi_rast_mask_forward(mi_rast_resize_fn geometry_buffer, void* geometry_user,
                          float tan_fovy, int prefiltered, float* out_mask, int* radii, int debug, int flags,
                          void* stream_, int* num_rendered)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (num_rendered) *num_rendered = 0;
     if (P <= 0 || width <= 0 || height <= 0) return fail(MI_RAST_ERR_INVALID, "P, width and height must be positive");
     if (!num_rendered || !radii || !out_mask || !mask) return fail(MI_RAST_ERR_INVALID, "null pointer");
-    const ViewParams vp = make_view(viewmatrix, projmatrix, nullptr, tan_fovx, tan_fovy, scale_modifier, width, height);
-    int rc;
-    GeomPtrs geom;
-    ImgPtrs img;
-    BinPtrs bin;
+    Call c{make_view(viewmatrix, projmatrix, nullptr, tan_fovx, tan_fovy, scale_modifier, width, height), (hipStream_t)stream_, debug, flags, P,
+           {}, {}, {}, 0u};
     // DEPTH/cuda_rasterizer/rasterizer_impl.cu:495-521: shs = nullptr, colours "given" (dummy pointer)
-    rc = geometry_and_binning(geometry_buffer, geometry_user, binning_buffer, binning_user, image_buffer, image_user, P,
-                              0, 0, width, height, means3D, nullptr, 1, opacities, scales, rotations, cov3D_precomp, vp,
-                              prefiltered, radii, debug, flags, stream, geom, img, bin, num_rendered);
-    if (rc) return rc;
+    const FrontArgs front{geometry_buffer, binning_buffer, image_buffer, geometry_user, binning_user, image_user, 0, 0, 1, prefiltered,
+                          means3D, nullptr, opacities, scales, rotations, cov3D_precomp, radii};
+    if (int rc = geometry_and_binning(c, front, num_rendered)) return rc;
     {
-        StageTimer t(stream, MI_STAGE_BLEND_FWD);
-        launch_blend_fwd<0, 1>(vp, stream, img, bin, geom, nullptr, mask, nullptr, nullptr, out_mask, nullptr, (flags & MI_RAST_FAST_EXP) == 0);
+        StageTimer t(c.stream, MI_STAGE_BLEND_FWD);
+        launch_blend_fwd<0, 1>(c, FwdArgs{0, nullptr, mask, nullptr, nullptr, out_mask, nullptr}, ChannelBlock{0, 0, 0});
     }
-    STAGE_CHECK("render_mask");
+    STAGE_CHECK(c, "render_mask");
     return MI_RAST_OK;
 }
 
 int mi_rast_mask_backward(int P, int R, int width, int height, char* geom_buffer, char* binning_buffer,
                           char* img_buffer, const float* dL_dout_mask, float* dL_dmask, int debug, int flags, void* stream_)
 {
-    hipStream_t stream = (hipStream_t)stream_;
     if (P <= 0) return MI_RAST_OK;
-    const ViewParams vp = make_blend_view(width, height);
-    const GeomPtrs geom = geom_from(geom_buffer, P);
-    const BinPtrs bin = bin_from(binning_buffer, R);
-    const ImgPtrs img = img_from(img_buffer, width, height);
+    const Call c{make_blend_view(width, height), (hipStream_t)stream_, debug, flags, P, geom_from(geom_buffer, P),
+                 img_from(img_buffer, width, height), bin_from(binning_buffer, R), 0u};
     {
-        StageTimer t(stream, MI_STAGE_BLEND_BWD);
-        HIP_TRY(hipMemsetAsync(geom.bwd_pack, 0, (size_t)P * 8 * sizeof(float), stream));
-        launch_blend_bwd<0, true>(vp, stream, img, bin, geom, nullptr, nullptr, nullptr, dL_dout_mask, nullptr, (flags & MI_RAST_FAST_EXP) == 0);
-        hipLaunchKernelGGL(unpack_mask_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, geom.bwd_pack, dL_dmask);
+        StageTimer t(c.stream, MI_STAGE_BLEND_BWD);
+        HIP_TRY(hipMemsetAsync(c.geom.bwd_pack, 0, (size_t)P * 8 * sizeof(float), c.stream));
+        launch_mask_bwd(c, dL_dout_mask);
+        hipLaunchKernelGGL(unpack_mask_kernel, dim3((P + 255) / 256), dim3(256), 0, c.stream, P, c.geom.bwd_pack, dL_dmask);
     }
-    STAGE_CHECK("render_mask backward");
+    STAGE_CHECK(c, "render_mask backward");
     return MI_RAST_OK;
 }
 

