@@ -255,6 +255,42 @@ int mi_rast_mask_backward(
     char* geom_buffer, char* binning_buffer, char* img_buffer,
     const float* dL_dout_mask, float* dL_dmask, int debug, int flags, void* stream);
 
+/* ---- 2D-to-3D score lifting (csrc/lift.h) ----
+ * EXTENSION: what the reference's clip_utils.get_3d_mask (clip_utils/__init__.py:291-330) computes per view through a mask render and
+ * its backward, in one front-to-back walk of the tile lists:
+ *     votes[g, k] += sum over the pixels p of  alpha_g(p) T_g(p) scores[k, p]          (k < K)
+ * with alpha and T exactly as the forward blends them (CF/cuda_rasterizer/forward.cu:330-356: power > 0 and alpha < 1/255 skip the
+ * pair; the pair that would take T below 1e-4 ends the pixel and is not blended).  That is dL_dcolors of mi_rast_backward with
+ * dL_dpix = scores, and for K = 1 dL_dmask of mi_rast_mask_backward with dL_dout_mask = scores; no image is rendered, and neither
+ * final_T nor n_contrib is read or written.
+ *   scores  [K, height, width], 1 <= K <= MI_RAST_LIFT_MAX_CHANNELS
+ *   votes   [P, K], ACCUMULATED into and never cleared by the library; rows of Gaussians that blend nowhere are not touched, so
+ *           one tensor sums the votes of any number of views.  The rows are added with float atomics: the last bits of the
+ *           result depend on the order in which they arrive.
+ * mi_rast_lift runs the stages in front of the blend exactly as mi_rast_mask_forward does (colours "given", no SHs), then the lift
+ * kernel; `flags`: MI_RAST_FULL_LISTS, MI_RAST_NO_CULL, MI_RAST_FAST_EXP, MI_RAST_EQUAL_RUNS.
+ * mi_rast_lift_reuse runs the lift kernel alone over the buffers that an earlier mi_rast_forward, mi_rast_mask_forward or
+ * mi_rast_lift of the SAME geometry, camera and list mode left behind (R: its num_rendered).  It only READS the three buffers, so
+ * it is legal between a forward and that forward's backward; `flags`: MI_RAST_FAST_EXP.
+ * Arguments are checked before any HIP call. */
+#define MI_RAST_LIFT_MAX_CHANNELS 64
+int mi_rast_lift(
+    mi_rast_resize_fn geometry_buffer, void* geometry_user,
+    mi_rast_resize_fn binning_buffer, void* binning_user,
+    mi_rast_resize_fn image_buffer, void* image_user,
+    int P, int K, int width, int height,
+    const float* means3D, const float* opacities,
+    const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+    const float* viewmatrix, const float* projmatrix,
+    float tan_fovx, float tan_fovy, int prefiltered,
+    const float* scores, float* votes,
+    int* radii, int debug, int flags, void* stream, int* num_rendered /* [host] */);
+
+int mi_rast_lift_reuse(
+    int P, int K, int R, int width, int height,
+    const char* geom_buffer, const char* binning_buffer, const char* img_buffer,
+    const float* scores, float* votes, int flags, void* stream);
+
 /* ---- introspection (used by the parity tests and bench.py; not part of the reference API) ---- */
 
 const char* mi_rast_last_error(void);

@@ -22,6 +22,9 @@ MI_STAGES = ["preprocess", "tile_scan", "emit", "tile_sort", "blend_fwd", "blend
 
 # include/mi_segment.h, its clustering section (csrc/mi_cluster.hip); listed on its own and as the tail of EXPORTS
 CLUSTER_EXPORTS = ["mi_cluster_workspace_bytes", "mi_cluster_core_distances", "mi_cluster_mst", "mi_cluster_mst_rounds", "mi_cluster_labels_host"]
+# include/mi_rast.h, its score-lifting section (csrc/lift.h); listed on its own and as the tail of EXPORTS
+LIFT_EXPORTS = ["mi_rast_lift", "mi_rast_lift_reuse"]
+MI_RAST_LIFT_MAX_CHANNELS = 64
 EXPORTS = [
     "mi_rast_forward", "mi_rast_forward_reuse", "mi_rast_last_longest_run", "mi_rast_fingerprint", "mi_rast_features_only_supported", "mi_rast_backward", "mi_rast_mark_visible", "mi_rast_mask_forward",
     "mi_rast_mask_backward", "mi_rast_last_error", "mi_rast_version", "mi_rast_supported_channels",
@@ -32,7 +35,7 @@ EXPORTS = [
     "mi_contrastive_forward", "mi_contrastive_backward",  # include/mi_contrastive.h
     "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
     "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
-] + CLUSTER_EXPORTS
+] + CLUSTER_EXPORTS + LIFT_EXPORTS
 MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_scales"]   # include/mi_mask_scales.h
 SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
@@ -96,6 +99,11 @@ def load():
                                        vp, vp, vp, vp, f, f, i, vp, vp, i, i, vp, C.POINTER(i)]
     L.mi_rast_mask_backward.restype = i
     L.mi_rast_mask_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, i, i, vp]
+    L.mi_rast_lift.restype = i
+    L.mi_rast_lift.argtypes = [RESIZE_FN, vp, RESIZE_FN, vp, RESIZE_FN, vp, i, i, i, i, vp, vp, vp, f, vp, vp, vp, vp, f, f, i,
+                               vp, vp, vp, i, i, vp, C.POINTER(i)]
+    L.mi_rast_lift_reuse.restype = i
+    L.mi_rast_lift_reuse.argtypes = [i, i, i, i, i, vp, vp, vp, vp, vp, i, vp]
     L.mi_rast_last_error.restype = C.c_char_p
     L.mi_rast_version.restype = C.c_char_p
     L.mi_rast_supported_channels.restype = i

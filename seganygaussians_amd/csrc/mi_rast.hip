@@ -25,6 +25,7 @@
 #endif
 #include "common.h"
 #include "geometry.h"
+#include "lift.h"             // 2D-to-3D score lifting (mi_rast_lift): one front-to-back walk, one wave per half tile
 
 using namespace mirast;
 
@@ -682,6 +683,36 @@ void launch_mask_bwd(const Call& c, const float* dL_dout_mask)
     });
 }
 
+// The lift kernel (lift.h) over all K score channels at once: the range scan's XCD runs dealt statically, 4 / LIFT_NQ items per tile
+template <int NB>
+void launch_lift(const Call& c, int K, const float* scores, float* votes)
+{
+    const uint32_t run = c.longest_run ? c.longest_run : xcd_max_run(c.ntiles());
+    with_bool(c.xexp(), [&](auto xexp) {
+        hipLaunchKernelGGL((lift_kernel<NB, decltype(xexp)::value>), dim3(8u * (4 / LIFT_NQ) * run), dim3(64), 0, c.stream, c.img.ranges,
+                           c.bin.blend_list, c.geom.index_rec, c.vp.W, c.vp.H, c.vp.grid_x, c.ntiles(), scores, votes, K, c.img.run_bounds);
+    });
+}
+int lift_stage(const Call& c, int K, const float* scores, float* votes)
+{
+    {
+        StageTimer t(c.stream, MI_STAGE_BLEND_FWD);
+        if (K <= 16) launch_lift<1>(c, K, scores, votes);
+        else if (K <= 32) launch_lift<2>(c, K, scores, votes);
+        else launch_lift<4>(c, K, scores, votes);
+    }
+    STAGE_CHECK(c, "lift");
+    return MI_RAST_OK;
+}
+// what mi_rast_lift and mi_rast_lift_reuse refuse alike
+int check_lift_args(int P, int K, int width, int height, const float* scores, const float* votes)
+{
+    if (P <= 0 || width <= 0 || height <= 0) return fail(MI_RAST_ERR_INVALID, "P, width and height must be positive");
+    if (K < 1 || K > MI_RAST_LIFT_MAX_CHANNELS) return fail(MI_RAST_ERR_INVALID, "lift: need 1 <= K <= 64 score channels");
+    if (!scores || !votes) return fail(MI_RAST_ERR_INVALID, "lift: null scores or votes");
+    return MI_RAST_OK;
+}
+
 }  // namespace
 
 #ifdef MI_RAST_PROFILING
@@ -1116,6 +1147,39 @@ int mi_rast_mask_backward(int P, int R, int width, int height, char* geom_buffer
     }
     STAGE_CHECK(c, "render_mask backward");
     return MI_RAST_OK;
+}
+
+// EXTENSION (include/mi_rast.h): per-Gaussian votes of K score images, the front half of mi_rast_mask_forward + the lift kernel
+int mi_rast_lift(mi_rast_resize_fn geometry_buffer, void* geometry_user, mi_rast_resize_fn binning_buffer, void* binning_user,
+                 mi_rast_resize_fn image_buffer, void* image_user, int P, int K, int width, int height, const float* means3D,
+                 const float* opacities, const float* scales, float scale_modifier, const float* rotations, const float* cov3D_precomp,
+                 const float* viewmatrix, const float* projmatrix, float tan_fovx, float tan_fovy, int prefiltered, const float* scores,
+                 float* votes, int* radii, int debug, int flags, void* stream_, int* num_rendered)
+{
+    if (num_rendered) *num_rendered = 0;
+    if (int rc = check_lift_args(P, K, width, height, scores, votes)) return rc;
+    if (!num_rendered || !radii) return fail(MI_RAST_ERR_INVALID, "null output pointer");
+    if (!geometry_buffer || !binning_buffer || !image_buffer) return fail(MI_RAST_ERR_INVALID, "lift: null buffer callback");
+    Call c{make_view(viewmatrix, projmatrix, nullptr, tan_fovx, tan_fovy, scale_modifier, width, height), (hipStream_t)stream_, debug, flags, P,
+           {}, {}, {}, 0u};
+    const FrontArgs front{geometry_buffer, binning_buffer, image_buffer, geometry_user, binning_user, image_user, 0, 0, 1, prefiltered,
+                          means3D, nullptr, opacities, scales, rotations, cov3D_precomp, radii};
+    if (int rc = geometry_and_binning(c, front, num_rendered)) return rc;
+    if (*num_rendered == 0) return MI_RAST_OK;   // no overlap: no Gaussian blends anywhere
+    return lift_stage(c, K, scores, votes);
+}
+
+int mi_rast_lift_reuse(int P, int K, int R, int width, int height, const char* geom_buffer, const char* binning_buffer,
+                       const char* img_buffer, const float* scores, float* votes, int flags, void* stream_)
+{
+    if (int rc = check_lift_args(P, K, width, height, scores, votes)) return rc;
+    if (R < 0) return fail(MI_RAST_ERR_INVALID, "lift: R must not be negative");
+    if (!geom_buffer || !binning_buffer || !img_buffer) return fail(MI_RAST_ERR_INVALID, "lift: null buffer");
+    if (R == 0) return MI_RAST_OK;
+    // (the field pointers are carved as the writers carve them; the lift kernel's parameters are pointers to const)
+    const Call c{make_blend_view(width, height), (hipStream_t)stream_, 0, flags, P, geom_from(const_cast<char*>(geom_buffer), P),
+                 img_from(const_cast<char*>(img_buffer), width, height), bin_from(const_cast<char*>(binning_buffer), R), 0u};
+    return lift_stage(c, K, scores, votes);
 }
 
 }  // extern "C"
