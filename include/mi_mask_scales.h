@@ -17,6 +17,8 @@
  *          (64 pixels per lane).  Otherwise each resampled value is PyTorch's CPU bilinear weight pair of 4 source bits and the
  *          3x3 window is summed in f32 in row-major order.
  *          Algorithmic bytes: 8 M (h Wq_in + H Wq) (31 MB read + 31 MB written at M = 120 and 1080p).
+ *          erode_min_sum is the same with the threshold as an argument (3x3 box sum >= min_sum; the notebook's language section has
+ *          2): erode is erode_min_sum at 5.  At the same size the count is an integer and the test is count >= ceil(min_sum).
  * scales : two launches.  eroded (M, H, W) packed, depth (H, W) f32, fx = (W/2) / tan(fovx/2), fy = (H/2) / tan(fovy/2) ->
  *          scales (M) f32 and counts (M) int64 (the eroded pixel count of each mask).  count < 2 gives NaN, as torch's std of 0
  *          or 1 rows.  Moments in f64; per-tile partials in the workspace, reduced in a fixed order: bit-identical across runs.
@@ -36,6 +38,9 @@ size_t mi_mask_scales_workspace_bytes(int M, int H, int W);
 
 int mi_mask_erode(int M, int h, int w, const unsigned long long* packed_in /* [M,h,ceil(w/64)] */, int H, int W,
                   unsigned long long* packed_out /* [M,H,ceil(W/64)] */, void* stream);
+
+int mi_mask_erode_min_sum(int M, int h, int w, const unsigned long long* packed_in /* [M,h,ceil(w/64)] */, int H, int W, float min_sum,
+                          unsigned long long* packed_out /* [M,H,ceil(W/64)] */, void* stream);
 
 int mi_mask_scales(int M, int H, int W, const unsigned long long* eroded /* [M,H,ceil(W/64)] */, const float* depth /* [H,W] */,
                    double fx, double fy, void* workspace, size_t workspace_bytes, float* scales /* [M] */, long long* counts /* [M] */,

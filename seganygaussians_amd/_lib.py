@@ -25,6 +25,8 @@ CLUSTER_EXPORTS = ["mi_cluster_workspace_bytes", "mi_cluster_core_distances", "m
 # include/mi_rast.h, its score-lifting section (csrc/lift.h); listed on its own and as the tail of EXPORTS
 LIFT_EXPORTS = ["mi_rast_lift", "mi_rast_lift_reuse"]
 MI_RAST_LIFT_MAX_CHANNELS = 64
+# include/mi_segment.h, its vote-graph section (csrc/mi_vote_graph.hip); listed on its own and as the tail of EXPORTS
+VOTE_GRAPH_EXPORTS = ["mi_vote_mask_features_workspace_bytes", "mi_vote_mask_features", "mi_vote_anchor_bits", "mi_vote_relevancy"]
 EXPORTS = [
     "mi_rast_forward", "mi_rast_forward_reuse", "mi_rast_last_longest_run", "mi_rast_fingerprint", "mi_rast_features_only_supported", "mi_rast_backward", "mi_rast_mark_visible", "mi_rast_mask_forward",
     "mi_rast_mask_backward", "mi_rast_last_error", "mi_rast_version", "mi_rast_supported_channels",
@@ -35,8 +37,9 @@ EXPORTS = [
     "mi_contrastive_forward", "mi_contrastive_backward",  # include/mi_contrastive.h
     "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
     "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
-] + CLUSTER_EXPORTS + LIFT_EXPORTS
-MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_scales"]   # include/mi_mask_scales.h
+] + CLUSTER_EXPORTS + LIFT_EXPORTS + VOTE_GRAPH_EXPORTS
+MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_erode_min_sum", "mi_mask_scales"]   # include/mi_mask_scales.h
+MI_VOTE_MAX_ANCHORS, MI_VOTE_MAX_EMBED_DIM, MI_VOTE_MAX_PROMPTS = 32768, 1024, 16
 SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
 PHOTOMETRIC_EXPORTS = ["mi_photo_loss_workspace_bytes", "mi_photo_loss_window", "mi_photo_loss_forward", "mi_photo_loss_backward"]   # include/mi_photometric.h
@@ -151,6 +154,8 @@ def load():
     L.mi_mask_scales_workspace_bytes.argtypes = [i, i, i]
     L.mi_mask_erode.restype = i
     L.mi_mask_erode.argtypes = [i, i, i, vp, i, i, vp, vp]
+    L.mi_mask_erode_min_sum.restype = i
+    L.mi_mask_erode_min_sum.argtypes = [i, i, i, vp, i, i, f, vp, vp]
     L.mi_mask_scales.restype = i
     L.mi_mask_scales.argtypes = [i, i, i, vp, vp, C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp]
     L.mi_segment_scores.restype = i
@@ -192,6 +197,14 @@ def load():
     L.mi_cluster_mst_rounds.argtypes = []
     L.mi_cluster_labels_host.restype = i
     L.mi_cluster_labels_host.argtypes = [i, i, vp, vp, vp, i, d, i, vp, C.POINTER(i)]
+    L.mi_vote_mask_features_workspace_bytes.restype = C.c_size_t
+    L.mi_vote_mask_features_workspace_bytes.argtypes = [i, i, i, i]
+    L.mi_vote_mask_features.restype = i
+    L.mi_vote_mask_features.argtypes = [i, i, i, i, vp, i, i, vp, vp, vp, C.c_size_t, vp, vp, vp]
+    L.mi_vote_anchor_bits.restype = i
+    L.mi_vote_anchor_bits.argtypes = [i, i, i, vp, vp, vp, f, vp, vp, vp]
+    L.mi_vote_relevancy.restype = i
+    L.mi_vote_relevancy.argtypes = [i, i, i, i, vp, i, vp, vp, i, vp, vp]
     _lib = L
     return L
 

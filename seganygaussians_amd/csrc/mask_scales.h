@@ -1,9 +1,10 @@
 // mask_scales.h -- SAM-mask 3-D scales: mask erosion and the per-mask point spread (include/mi_mask_scales.h; DESIGN.md section 15;
 // reference: get_scale.py:128-159).
 //
-//   erode (same size) : one lane per output word.  The bilinear resampling is the identity, so "3x3 box sum >= 5" is the majority of
+//   erode (same size) : one lane per output word.  The bilinear resampling is the identity, so "3x3 box sum >= k" is a count of
 //                       9 bits: the three rows' west / centre / east bits (neighbour bits across word seams from the adjacent words)
-//                       go through a carry-save adder tree, 64 pixels per lane.
+//                       go through a carry-save adder tree, 64 pixels per lane, and the 4-bit count is compared with k bit-sliced
+//                       (k = 5, the majority, for mi_mask_erode).
 //   erode (resampled) : one wave per output word, one lane per pixel.  Each of the 9 window values is PyTorch's CPU bilinear
 //                       interpolation of 4 source bits (upsample_bilinear2d, align_corners=False), summed in f32 in row-major order;
 //                       __ballot packs the 64 results.
@@ -29,8 +30,8 @@ __device__ inline uint64_t ms_valid_bits(int W, int q)
     return n >= 64 ? ~0ull : ((1ull << n) - 1ull);
 }
 
-// ---- erode, same size: bit-sliced majority of the 3x3 window -----------------------------------------------------------------
-__global__ void __launch_bounds__(MS_THREADS) ms_erode_same_kernel(int M, int H, int W, int Wq, const uint64_t* __restrict__ in,
+// ---- erode, same size: bit-sliced "count of the 3x3 window >= k", 0 <= k <= 15 -------------------------------------------------
+__global__ void __launch_bounds__(MS_THREADS) ms_erode_same_kernel(int M, int H, int W, int Wq, const uint64_t* __restrict__ in, int k,
                                                                    uint64_t* __restrict__ out)
 {
     const size_t i = (size_t)blockIdx.x * MS_THREADS + threadIdx.x;
@@ -60,8 +61,16 @@ __global__ void __launch_bounds__(MS_THREADS) ms_erode_same_kernel(int M, int H,
     const uint64_t u4 = (c[0] & c[1]) | (c[2] & (c[0] ^ c[1]));              // weight 4
     const uint64_t v2 = u2 ^ t2, v4 = u2 & t2;                               // weight 2, 4
     const uint64_t w4 = u4 ^ v4, w8 = u4 & v4;                               // weight 4, 8
-    // sum = t1 + 2 v2 + 4 w4 + 8 w8 >= 5
-    out[i] = (w8 | (w4 & (t1 | v2))) & ms_valid_bits(W, q);
+    // sum = t1 + 2 v2 + 4 w4 + 8 w8 >= k, from the top bit down: greater where the sum has a bit k lacks and all above agree
+    const uint64_t bit[4] = {t1, v2, w4, w8};
+    uint64_t gt = 0ull, eq = ~0ull;
+#pragma unroll
+    for (int b = 3; b >= 0; b--) {
+        const uint64_t kb = ((k >> b) & 1) ? ~0ull : 0ull;
+        gt |= eq & bit[b] & ~kb;
+        eq &= ~(bit[b] ^ kb);
+    }
+    out[i] = (gt | eq) & ms_valid_bits(W, q);
 }
 
 // ---- erode, resampled: PyTorch's CPU bilinear weights (UpSampleKernel.cpp, align_corners=False) --------------------------------
@@ -84,7 +93,7 @@ __device__ inline float ms_bit(const uint64_t* __restrict__ row, int x) { return
 
 __global__ void __launch_bounds__(MS_THREADS) ms_erode_resample_kernel(int M, int h, int w, int Wqi, const uint64_t* __restrict__ in,
                                                                        int H, int W, int Wq, float scale_h, float scale_w,
-                                                                       uint64_t* __restrict__ out)
+                                                                       float min_sum, uint64_t* __restrict__ out)
 {
     const size_t i = (size_t)blockIdx.x * (MS_THREADS / 64) + (threadIdx.x >> 6);   // one wave per output word
     if (i >= (size_t)M * H * Wq) return;                                             // wave-uniform
@@ -117,7 +126,7 @@ __global__ void __launch_bounds__(MS_THREADS) ms_erode_resample_kernel(int M, in
             }
         }
     }
-    const uint64_t word = __ballot(x < W && box >= 5.f);
+    const uint64_t word = __ballot(x < W && box >= min_sum);
     if (lane == 0) out[i] = word;
 }
 

@@ -26,28 +26,37 @@ size_t mi_mask_scales_workspace_bytes(int M, int H, int W)
     return (size_t)M * ms_tiles(H, W) * MS_STATS * sizeof(double);
 }
 
-int mi_mask_erode(int M, int h, int w, const unsigned long long* packed_in, int H, int W, unsigned long long* packed_out, void* stream_)
+int mi_mask_erode_min_sum(int M, int h, int w, const unsigned long long* packed_in, int H, int W, float min_sum,
+                          unsigned long long* packed_out, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = ms_check(M, h, w, "h, w")) return rc;
     if (int rc = ms_check(M, H, W, "H, W")) return rc;
     if (!packed_in || !packed_out) return fail(MI_RAST_ERR_INVALID, "mask scales: null pointer");
+    if (!(min_sum == min_sum)) return fail(MI_RAST_ERR_INVALID, "mask scales: min_sum is NaN");
     const int Wqi = (w + 63) / 64, Wq = (W + 63) / 64;
     const size_t in_words = (size_t)M * h * Wqi, words = (size_t)M * H * Wq;
     if (packed_out < packed_in + in_words && packed_in < packed_out + words)
         return fail(MI_RAST_ERR_INVALID, "mask scales: the eroded masks must not overlap the input masks");
     if (h == H && w == W) {
+        // the window holds an integer 0 .. 9: count >= min_sum is count >= ceil(min_sum); 10 is "never"
+        const int k = min_sum <= 0.f ? 0 : min_sum > 9.f ? 10 : (int)ceilf(min_sum);
         hipLaunchKernelGGL(ms_erode_same_kernel, dim3((unsigned)((words + MS_THREADS - 1) / MS_THREADS)), dim3(MS_THREADS), 0, stream,
-                           M, H, W, Wq, (const uint64_t*)packed_in, (uint64_t*)packed_out);
+                           M, H, W, Wq, (const uint64_t*)packed_in, k, (uint64_t*)packed_out);
     } else {
         // area_pixel_compute_scale (align_corners=False, no scale factor): (float)in / out
         const float scale_h = (float)h / (float)H, scale_w = (float)w / (float)W;
         constexpr int wpb = MS_THREADS / 64;
         hipLaunchKernelGGL(ms_erode_resample_kernel, dim3((unsigned)((words + wpb - 1) / wpb)), dim3(MS_THREADS), 0, stream,
-                           M, h, w, Wqi, (const uint64_t*)packed_in, H, W, Wq, scale_h, scale_w, (uint64_t*)packed_out);
+                           M, h, w, Wqi, (const uint64_t*)packed_in, H, W, Wq, scale_h, scale_w, min_sum, (uint64_t*)packed_out);
     }
     HIP_TRY(hipGetLastError());
     return MI_RAST_OK;
+}
+
+int mi_mask_erode(int M, int h, int w, const unsigned long long* packed_in, int H, int W, unsigned long long* packed_out, void* stream)
+{
+    return mi_mask_erode_min_sum(M, h, w, packed_in, H, W, 5.f, packed_out, stream);
 }
 
 int mi_mask_scales(int M, int H, int W, const unsigned long long* eroded, const float* depth, double fx, double fy, void* workspace,

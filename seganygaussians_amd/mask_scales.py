@@ -5,8 +5,8 @@ training view the reference moves the rendered depth to the CPU, back-projects e
 the depth's size, erodes them (3x3 box sum >= 5) and takes (points[mask].std(dim=0) * 2).norm() per mask.  Here the masks stay
 bit-packed on the device, in the PackedSamMasks layout the targets kernels read (pack_sam_masks):
 
-  * erode_sam_masks() -- one launch.  At the same size the erosion is the bit-sliced majority of the 3x3 window; otherwise each
-    window value is PyTorch's CPU bilinear interpolation of 4 source bits, summed in f32.
+  * erode_sam_masks() -- one launch.  At the same size the erosion is the bit-sliced count of the 3x3 window (>= 5: its majority);
+    otherwise each window value is PyTorch's CPU bilinear interpolation of 4 source bits, summed in f32.  min_sum sets the threshold.
   * sam_mask_scales() -- the erosion, then per-tile f64 moments and a fixed-order reduction: counts exact, scales deterministic.
 
 The reference's quirks are kept (DESIGN.md section 15): x pairs the row index with W/2 and fx, y the column index with H/2 and fy;
@@ -54,7 +54,7 @@ def _size(size, who: str):
     return H, W
 
 
-def _erode(packed: PackedSamMasks, H: int, W: int) -> PackedSamMasks:
+def _erode(packed: PackedSamMasks, H: int, W: int, min_sum: float = 5.0) -> PackedSamMasks:
     from . import _lib
     L = _lib.load()
     M, h, w = packed.shape
@@ -63,20 +63,31 @@ def _erode(packed: PackedSamMasks, H: int, W: int) -> PackedSamMasks:
         raise ValueError("erode_sam_masks: more than 2^31 mask words")
     out = torch.empty((M, H, (W + 63) // 64), device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
-        check(L.mi_mask_erode(M, h, w, packed.words.data_ptr(), H, W, out.data_ptr(), stream_ptr(dev)))
+        check(L.mi_mask_erode_min_sum(M, h, w, packed.words.data_ptr(), H, W, min_sum, out.data_ptr(), stream_ptr(dev)))
     return PackedSamMasks(out, (M, H, W))
 
 
-def erode_sam_masks(masks, size) -> PackedSamMasks:
+def _min_sum(min_sum, who: str) -> float:
+    try:
+        v = float(min_sum)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: min_sum must be a number, got {min_sum!r}") from None
+    if v != v:
+        raise ValueError(f"{who}: min_sum is NaN")
+    return v
+
+
+def erode_sam_masks(masks, size, min_sum=5) -> PackedSamMasks:
     """get_scale.py:145-152: F.interpolate(masks[:, None], size, mode='bilinear', align_corners=False), conv2d with a 3x3 box of
-    ones (zero padding) and >= 5, bit-packed.
+    ones (zero padding) and >= min_sum (5 there; the notebook's language section has 2), bit-packed.
 
     masks: bool (M, h, w) on the CPU or a GPU (packed here), or a PackedSamMasks (padding bits 0, as pack_sam_masks writes them);
     size: the output (H, W).  Returns the eroded masks as a PackedSamMasks (M, H, ceil(W / 64)) on the masks' GPU (the current GPU
     for CPU masks), padding bits 0."""
     H, W = _size(size, "erode_sam_masks")
+    min_sum = _min_sum(min_sum, "erode_sam_masks")
     packed = _as_packed(masks, None, "erode_sam_masks")
-    return _erode(packed, H, W)
+    return _erode(packed, H, W, min_sum)
 
 
 def sam_mask_scales(depth: torch.Tensor, masks, fovx: float, fovy: float, return_counts: bool = False):
