@@ -86,7 +86,7 @@ extern "C" {
 #define MI_RAST_F32_BLEND 2    /* 32/64-channel forward on the f32 FMA-chain kernel instead of the exactly split bf16x3
                                   matrix kernel (same alpha/T/n_contrib bit for bit; images agree to a few ulp) */
 #define MI_RAST_EQUAL_RUNS 256 /* A/B aid: both blend kernels give every XCD (its own L2) one contiguous run of tiles; by default the runs
-                                  are cut at equal MODELLED work -- sum over the tiles of min(list length, 768) + 128, csrc/binning.h:
+                                  are cut at equal MODELLED work -- sum over the tiles of min(list length, 768) + 128, csrc/tile_ranges.h:
                                   tile_ranges_kernel -- because the dispatcher deals workgroups to the XCDs whatever their progress and
                                   real scenes' density varies over the image; with this flag at equal tile counts (rounds 2-4).
                                   Results are the same either way (the order of the atomic sums apart) */

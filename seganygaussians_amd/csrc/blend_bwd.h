@@ -16,9 +16,9 @@
 //    those below ITS quadrant's maximum, and entries are culled per quadrant exactly as in the forward (cull.h).
 #pragma once
 
-#include "blend_fwd.h"
+#include "blend_rec.h"
 #include "common.h"
-#include "cull.h"
+#include "wave.h"
 
 namespace mirast {
 
@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256) mask_bwd_kernel(
     if (Lt == 0) return;
     // blend-list records the forward walked for this tile: a superset of every contributing entry
     const int NS = (int)tile_nsurv[tile];
-    const uint32_t* lst = blend_list + range.x;   // four-byte entries; list_record (binning.h) gathers the geometry record of one
+    const uint32_t* lst = blend_list + range.x;   // four-byte entries; list_record (blend_rec.h) gathers the geometry record of one
 
     float T = inside ? final_Ts[pix_id] : 0;
     // (clamped address + select: no branch)

@@ -19,8 +19,10 @@
 
 #include "blend_bwd_shared.h"
 #include "blend_bwd_wave.h"
-#include "blend_fwd.h"
+#include "blend_rec.h"
 #include "common.h"
+#include "wave.h"
+#include "xcd_runs.h"
 
 namespace mirast {
 
@@ -31,7 +33,7 @@ __global__ void __launch_bounds__(64, C == 64 ? 2 : 3) blend_bwd_feat_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ blend_list, const BlendRec* __restrict__ index_rec,
     const uint32_t* __restrict__ tile_nsurv, int W, int H, uint32_t horizontal_blocks, uint32_t ntiles,
     const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpixels,
-    float* __restrict__ dL_dcolors, uint32_t* __restrict__ queue_ctr /* eight zeroed work-queue counters (common.h: xcd_grab) */,
+    float* __restrict__ dL_dcolors, uint32_t* __restrict__ queue_ctr /* eight zeroed work-queue counters (xcd_runs.h: xcd_grab_runs) */,
     int cstride_arg, const uint32_t* __restrict__ run_bounds /* [9]: the XCDs' runs of tiles, left in the image buffer by the forward */)
 {
     static_assert(C == 16 || C == 32 || C == 64, "16-, 32- and 64-channel blocks");

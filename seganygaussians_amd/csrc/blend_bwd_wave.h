@@ -9,7 +9,7 @@
 // were padding, the waves of a tile met at two barriers per batch (14 % of wave time), and a wave with few rows idled
 // while the tile's busiest quadrant worked.  Here a workgroup IS one wave:
 //   * the wave scans the tile's blend list itself, 64 entries at a time (four bytes each: Gaussian id | quadrant mask << 28,
-//     binning.h; prefetched one block ahead), and appends the entries of its quadrant to a ring in LDS (128 entries = 8 chunks
+//     blend_rec.h; prefetched one block ahead), and appends the entries of its quadrant to a ring in LDS (128 entries = 8 chunks
 //     of run-ahead), so chunks are always full -- only the wave's very last chunk is padded;
 //   * the 16 rows of the NEXT chunk (one 8-byte quarter of the geometry record index_rec[id] per lane + two float4 feature
 //     parts per lane, both gathered by the id) are requested before the current chunk is processed and wait in registers;
@@ -23,8 +23,11 @@
 #include <type_traits>
 
 #include "blend_bwd_shared.h"
-#include "blend_fwd.h"
+#include "blend_rec.h"
 #include "common.h"
+#include "wave.h"
+#include "xcd_runs.h"
+#include "xcd_stamp.h"
 
 namespace mirast {
 
@@ -61,11 +64,11 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
     const float* __restrict__ colors, const float* __restrict__ final_Ts, const uint32_t* __restrict__ n_contrib,
     const float* __restrict__ dL_dpixels, const float* __restrict__ dL_dout_mask,
     float* __restrict__ gpack /*[P,8] packed field gradients*/, float* __restrict__ dL_dcolors,
-    uint32_t* __restrict__ queue_ctr /* eight zeroed work-queue counters (common.h: xcd_grab) */,
+    uint32_t* __restrict__ queue_ctr /* eight zeroed work-queue counters (xcd_runs.h: xcd_grab_runs) */,
     int cstride_arg /* STRIDED: floats between the rows of two Gaussians in `colors` and `dL_dcolors` = the full channel count of
                        the feature this launch handles one channel block of (both pointers then point at the block) */,
     int cr_arg /* CR == 0: channels of this block that exist in memory */,
-    const uint32_t* __restrict__ run_bounds /* [9]: the XCDs' runs of tiles (common.h: XcdRuns), left in the image buffer by the forward */)
+    const uint32_t* __restrict__ run_bounds /* [9]: the XCDs' runs of tiles (xcd_runs.h: XcdRuns), left in the image buffer by the forward */)
 {
     constexpr int FROW = BwvCfg<C>::FROW, QCAP = BwvCfg<C>::QCAP, FEAT4 = BwvCfg<C>::FEAT4;
     const int cstride = STRIDED ? cstride_arg : CR;   // (a compile-time constant in the common case: no 64-bit multiply, no extra registers)
@@ -122,7 +125,7 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
     // List positions (n_contrib's unit) are indices into the tile's blend list: no entry at index >= wave_Lt can reach this quadrant.
     const int NS = min(NS_tile, wave_Lt);   // 0: nothing blended into this quadrant -- the wave leaves after the staging
     // below (not here: with an exit in between, hipcc sinks the gradient-image loads behind it, i.e. behind this wait)
-    // entry = Gaussian id | quadrant mask << 28 (binning.h); entry j of the walk (back to front) is lst[NS - 1 - j]
+    // entry = Gaussian id | quadrant mask << 28 (blend_rec.h); entry j of the walk (back to front) is lst[NS - 1 - j]
     const uint32_t* lst = NS > 0 ? blend_list + range.x : blend_list;
 
     // first scan block.  Scan loads are unconditional (clamped index): a conditional assignment makes hipcc copy the
@@ -526,13 +529,13 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
     };
 
     {
-        // workgroup -> (tile, quadrant).  Every XCD works through a contiguous run of tiles (common.h), and the four
+        // workgroup -> (tile, quadrant).  Every XCD works through a contiguous run of tiles (xcd_runs.h), and the four
         // quadrants of a tile go to four of its waves at about the same time: the records, the feature rows and the gradient
         // lines that the quadrants of a tile AND neighbouring tiles share stay in one L2.  The first half of a run
         // is assigned by the workgroup id (id = 8 (4 j + quad) + x: XCD x, j-th tile of its run); the items of the second
         // half are TAKEN from the XCD's queue, and from the other XCDs' queues when that one is empty (xcd_grab): the
         // runs stay contiguous while the XCDs keep pace, and nobody idles when the scene's density does not let them.
-        // The runs are work-balanced (common.h): nine boundaries in the image buffer; the grid is sized for the longest run the
+        // The runs are work-balanced (xcd_runs.h): nine boundaries in the image buffer; the grid is sized for the longest run the
         // clamp allows, ids beyond a run's static part and takers beyond the queued items leave at once.
         const uint32_t b = blockIdx.x, nstatic = 32u * xcd_static_len_max(ntiles);
         uint32_t item;
@@ -544,7 +547,7 @@ __global__ void __launch_bounds__(64, BwvCfg<C>::WAVES) blend_bwd_wave_kernel(
             item = xcd_grab_runs(queue_ctr, xcd_load_runs(run_bounds), 4u);
         }
         if (item != 0xFFFFFFFFu) {
-            MI_XCD_STAMP(false);   // (profiling build: per-XCD start / end stamps, blend_fwd.h)
+            MI_XCD_STAMP(false);   // (profiling build: per-XCD start / end stamps, xcd_stamp.h)
             quadrant(item >> 2, item & 3u);
             MI_XCD_STAMP(true);
         }

@@ -6,9 +6,9 @@
 //
 // gfx950 mapping: one 256-thread workgroup per 16x16 tile (the tile size is part of the integer
 // contract), four wave64s each owning an 8x8 pixel quadrant.  The kernel does not walk the raw tile list:
-// it streams the tile's BLEND LIST (binning.h), i.e. only the entries that can reach alpha >= 1/255
+// it streams the tile's BLEND LIST (tile_sort.h), i.e. only the entries that can reach alpha >= 1/255
 // somewhere in the tile (about one third of the list on the benchmark scene): four-byte entries id | quadrant mask,
-// each completed by ONE gather of the Gaussian's 32-byte geometry record (xy / conic / opacity; binning.h: list_record).
+// each completed by ONE gather of the Gaussian's 32-byte geometry record (xy / conic / opacity; blend_rec.h: list_record).
 // Per batch of FB records:
 //   A. record -> LDS; the NEXT batch's record is already in flight in registers while this one is blended;
 //   B. the C feature floats of every record are staged into LDS with coalesced 16-B loads (8 lanes cover one
@@ -23,33 +23,12 @@
 // Early termination is per wave (ballot) and per workgroup (__syncthreads_and).
 #pragma once
 
-#include "binning.h"
+#include "blend_rec.h"
 #include "common.h"
-
-// Per-wave time stamps of the blend kernels, PROFILING build only (tools/xcd_stamps.py; mi_rast_xcd_stamps in mi_rast.hip): a wave's
-// first lane stores the constant 100-MHz clock at its start (with the XCD it runs on) and at its end into ITS OWN two words -- plain
-// stores: stamps kept with atomics on sixteen shared words slowed the kernels by half.  The product build compiles the macro to nothing.
-// Here, not in common.h: g_xcd_log is a plain __device__ array, and of the library's translation units only mi_rast.hip may define it.
-#ifdef MI_RAST_PROFILING
-constexpr unsigned MI_XCD_LOG_WAVES = 1u << 18;
-__device__ unsigned long long g_xcd_log[2 * MI_XCD_LOG_WAVES];   // [2 b] = start << 3 | XCD, [2 b + 1] = end, b = workgroup id
-#define MI_XCD_STAMP(AT_END)                                                                                          \
-    do {                                                                                                              \
-        if ((threadIdx.x & 63) == 0 && blockIdx.x < MI_XCD_LOG_WAVES) {                                               \
-            const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                                           \
-            const unsigned x_ = __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 7u; /* HW_REG_XCC_ID */        \
-            g_xcd_log[2u * blockIdx.x + ((AT_END) ? 1u : 0u)] = (AT_END) ? t_ : ((t_ << 3) | x_);                     \
-        }                                                                                                             \
-    } while (0)
-#else
-#define MI_XCD_STAMP(AT_END) \
-    do {                     \
-    } while (0)
-#endif
+#include "wave.h"
 
 namespace mirast {
 
-constexpr int BATCH = 256;  // threads per tile workgroup
 constexpr int FB = 128;     // blend-list records per forward batch
 
 template <int CE>
@@ -112,7 +91,7 @@ __global__ void __launch_bounds__(256, (C == 32 && EXTRA == 0) ? 4 : 1) blend_fw
     const uint2 range = ranges[tile];
     const int list_len = (int)(range.y - range.x);
     const int ns_total = list_len;
-    const uint32_t* lst = blend_list + range.x;   // four-byte entries; list_record (binning.h) gathers the geometry record of one
+    const uint32_t* lst = blend_list + range.x;   // four-byte entries; list_record (blend_rec.h) gathers the geometry record of one
 
     float T = 1.0f;
     uint32_t last_contributor = 0;

@@ -19,14 +19,18 @@
 
 #include <type_traits>
 
-#include "blend_fwd.h"
 #include "blend_fwd_split.h"
+#include "blend_rec.h"
+#include "common.h"
+#include "wave.h"
+#include "xcd_runs.h"
+#include "xcd_stamp.h"
 
 namespace mirast {
 
 // workgroup -> (tile, quadrant): every XCD works through ONE contiguous run of tiles, the four quadrants of a tile on four of its
-// waves at about the same time (common.h; id = 8 (4 j + quad) + x: XCD x, j-th tile of its run).  The boundaries are the ones the
-// range scan left in the image buffer (binning.h: tile_ranges_kernel, runs of equal MODELLED work: what a tile costs varies over the
+// waves at about the same time (xcd_runs.h; id = 8 (4 j + quad) + x: XCD x, j-th tile of its run).  The boundaries are the ones the
+// range scan left in the image buffer (tile_ranges.h: tile_ranges_kernel, runs of equal MODELLED work: what a tile costs varies over the
 // image of a real scene, and a fast XCD cannot take more -- the dispatcher deals workgroup b to XCD b % 8 whatever their progress;
 // profiles/r04_xcd_balance.md, r05_xcd_balance.md); the grid is sized for the longest run, ids beyond a run's length have no item.
 __device__ __forceinline__ bool fwd_wave_item(uint32_t b, const uint32_t* __restrict__ run_bounds, uint32_t& tile, uint32_t& quad)
@@ -95,7 +99,7 @@ __global__ void __launch_bounds__(64, C == 32 ? FWD_WAVES32 : FWD_WAVES64) blend
     fwd_zero_fill(zfill, blockIdx.x, gridDim.x, (int)(threadIdx.x & 63));   // (every workgroup, also those without an item)
     uint32_t tile, quad;
     if (!fwd_wave_item(blockIdx.x, run_bounds, tile, quad)) return;
-    MI_XCD_STAMP(false);   // (profiling build: per-XCD start / end stamps, blend_fwd.h)
+    MI_XCD_STAMP(false);   // (profiling build: per-XCD start / end stamps, xcd_stamp.h)
     const int lane = threadIdx.x & 63;
     const uint32_t tile_x = tile % horizontal_blocks, tile_y = tile / horizontal_blocks;
     const uint32_t px = tile_x * TILE_X + (quad & 1) * 8 + (lane & 7);
@@ -109,7 +113,7 @@ __global__ void __launch_bounds__(64, C == 32 ? FWD_WAVES32 : FWD_WAVES64) blend
     const int list_len = (int)(range.y - range.x);
     const bool any_inside = ballot64(inside) != 0;
     const int ns = any_inside ? list_len : 0;
-    const uint32_t* lst = blend_list + range.x;   // entry = Gaussian id | quadrant mask << 28 (binning.h); its position is its index
+    const uint32_t* lst = blend_list + range.x;   // entry = Gaussian id | quadrant mask << 28 (blend_rec.h); its position is its index
 
     float T = 1.0f;
     uint32_t last_contributor = 0;
@@ -453,7 +457,7 @@ __global__ void __launch_bounds__(64, 8) blend_fwd_wave_rgb_kernel(
     const int list_len = (int)(range.y - range.x);
     const bool any_inside = ballot64(inside) != 0;
     const int ns = any_inside ? list_len : 0;
-    const uint32_t* lst = blend_list + range.x;   // entry = Gaussian id | quadrant mask << 28 (binning.h); its position is its index
+    const uint32_t* lst = blend_list + range.x;   // entry = Gaussian id | quadrant mask << 28 (blend_rec.h); its position is its index
 
     float T = 1.0f;
     uint32_t last_contributor = 0;

@@ -21,8 +21,10 @@
 // B (features) is gathered per lane from the staged rows: lane (channel n, k half) reads 8 bf16 per term.
 #pragma once
 
-#include "blend_fwd.h"
 #include "blend_fwd_split.h"
+#include "blend_rec.h"
+#include "common.h"
+#include "wave.h"
 
 namespace mirast {
 

@@ -10,7 +10,7 @@
 #pragma once
 
 #include "../../include/mi_contrastive.h"
-#include "common.h"
+#include "wave.h"
 
 namespace mirast {
 

@@ -17,7 +17,8 @@
 #pragma once
 
 #include "../../include/mi_contrastive.h"
-#include "common.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace mirast {
 
@@ -63,7 +64,7 @@ __global__ void __launch_bounds__(CL_THREADS) cl_cover_kernel(int M, int H, int 
         cov |= wd;
         int c = __popcll(wd);
 #pragma unroll
-        for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off);
+        for (int off = 32; off; off >>= 1) c += __shfl_xor(c, off);   // (not wave.h's wave_sum: the kernel's code would change)
         if (lane == 0 && c) atomicAdd(&area[m], (unsigned long long)c);
     }
     if (!live) return;
@@ -143,7 +144,7 @@ __device__ __forceinline__ bool cl_gt(const uint64_t* __restrict__ gh, const uin
 template <typename T>
 __device__ __forceinline__ void cl_block_sum(T* vals, int nvals, T* sm /* [CL_THREADS * nvals] */)
 {
-    // fixed-order tree over the workgroup's threads: the same inputs give the same bits
+    // fixed-order tree over the workgroup's threads: the same inputs give the same bits (an LDS tree, not wave.h's butterfly: another order)
     for (int k = 0; k < nvals; k++) sm[k * CL_THREADS + threadIdx.x] = vals[k];
     __syncthreads();
     for (int off = CL_THREADS / 2; off > 0; off >>= 1) {

@@ -12,7 +12,7 @@
 // contributor indices are preserved.
 //
 // The decision is taken per 8-pixel BAND of rows, in closed form (band_columns below): the binning pass of the lean lists
-// (binning.h: bin_spans_kernel) never looks at a tile that has no quadrant to keep.
+// (bin_lean.h: bin_spans_kernel) never looks at a tile that has no quadrant to keep.
 #pragma once
 
 #include "common.h"
@@ -63,7 +63,7 @@ __device__ __forceinline__ void shrink_rect(float2 xy, float4 co, int rad, uint2
 // dy the ellipse spans dx in [r-(dy), r+(dy)], r+-(dy) = (-B dy +- sqrt(2 tau A - det dy^2)) / A; r+ is concave with its
 // maximum at the ellipse's rightmost point dy* = -B ex / C (ex = sqrt(2 tau C / det)), so over the band it peaks at dy*
 // clamped into the band; r- mirrored.  One evaluation per (Gaussian, band) replaces the per-tile and per-quadrant box tests
-// above: the quadrant mask of a tile is read off the column intervals of its two bands (binning.h: bin_spans_kernel).
+// above: the quadrant mask of a tile is read off the column intervals of its two bands (bin_lean.h: bin_spans_kernel).
 // Conservative like shrink_rect: tau carries the same margin (3e-5 of the largest magnitude the terms of `power` reach
 // anywhere in the rect, + 2e-4), the extents 0.1 % + 0.01 px of slack -- far above the float rounding of this closed form
 // and of the kernels' own `power`; tests/test_row_spans.py checks the superset property pixel by pixel on the CPU and

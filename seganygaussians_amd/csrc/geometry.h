@@ -6,8 +6,9 @@
 // contiguous 768-B span, so every fetched line is fully used.
 #pragma once
 
-#include "binning.h"
+#include "blend_rec.h"
 #include "common.h"
+#include "wave.h"
 
 namespace mirast {
 
@@ -113,7 +114,7 @@ __device__ __forceinline__ float3 computeColorFromSH(int idx, int deg, const flo
 // Forward preprocess: CF/cuda_rasterizer/forward.cu:159-259 (+ in_frustum, auxiliary.h:139-164).
 // `culled_prefiltered` is incremented when prefiltered is set and a point is culled (the reference
 // printf+__trap()s the whole context there; we report an error instead).
-// gfx950 additions (binning.h): writes the 32-bit depth sort key (0xFFFFFFFF for culled Gaussians) and accumulates R = sum of tiles_touched of the visible Gaussians.
+// gfx950 additions (for bin_full.h / bin_lean.h and tile_ranges.h): writes the 32-bit depth sort key (0xFFFFFFFF for culled Gaussians) and accumulates R = sum of tiles_touched of the visible Gaussians.
 __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
     int P, int D, int M, const float* __restrict__ orig_points, const float* __restrict__ scales,
     const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
@@ -125,9 +126,9 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
     uint32_t band_h, uint32_t nbands, uint32_t* __restrict__ tile_total, uint32_t ntiles)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    __shared__ uint32_t s_band[MAX_BANDS];   // Gaussians of this workgroup per band of tile rows (binning.h: lean count / emit passes)
+    __shared__ uint32_t s_band[MAX_BANDS];   // Gaussians of this workgroup per band of tile rows (bin_lean.h)
     if (threadIdx.x < MAX_BANDS) s_band[threadIdx.x] = 0u;
-    if ((uint32_t)idx < ntiles) tile_total[idx] = 0u;   // per-tile entry counts: the count pass adds to them (binning.h); P < tiles: host memset
+    if ((uint32_t)idx < ntiles) tile_total[idx] = 0u;   // per-tile entry counts: the count pass adds to them (bin_lean.h); P < tiles: host memset
     // SH colours (forward.cu:23-74 reads 3 M floats per Gaussian, 192 bytes at degree 3): a thread walking its own row makes
     // every load instruction of the wave touch 64 rows 192 bytes apart.  The workgroup's rows are one contiguous block of
     // memory: staged into LDS with coalesced 16-byte loads (culled Gaussians included: 25 % more bytes, all of them streamed),
@@ -210,7 +211,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
             // everything the binning stages need of this Gaussian in one 32-byte record (depth_sort.h gathers it once)
             BlendRec rec;
             rec.xy = point_image;
-            rec.id = my_key;   // the depth bits ride in the record (binning.h: BlendRec)
+            rec.id = my_key;   // the depth bits ride in the record (blend_rec.h: BlendRec)
             rec.pm = (uint32_t)my_radii;
             rec.co = make_float4(conic.x, conic.y, conic.z, opacities[idx]);
             index_rec[idx] = rec;
@@ -253,7 +254,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
         uint32_t inv_min = my_key == 0xFFFFFFFFu ? 0u : ~my_key, mx = my_key == 0xFFFFFFFFu ? 0u : my_key;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {
-            sum += (uint32_t)__shfl_xor((int)sum, o, 64);
+            sum += (uint32_t)__shfl_xor((int)sum, o, 64);   // (sum and both maxima share the butterfly's steps: not wave.h's wave_sum)
             inv_min = max(inv_min, (uint32_t)__shfl_xor((int)inv_min, o, 64));
             mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
         }

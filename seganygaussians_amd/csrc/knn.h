@@ -18,10 +18,7 @@
 // ascending, ties by index.
 #pragma once
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "common.h"
+#include "wave.h"
 
 namespace mirast {
 
@@ -139,7 +136,7 @@ __global__ void __launch_bounds__(1024) knn_scan_kernel(int count, uint32_t* __r
         const uint32_t v = i < count ? data[i] : 0u;
         uint32_t inc = v;
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
+        for (int o = 1; o < 64; o <<= 1) {   // (not wave.h's wave_inclusive_scan: the kernel's code would change)
             const uint32_t t = (uint32_t)__shfl_up((int)inc, o, 64);
             if (lane >= o) inc += t;
         }

@@ -12,7 +12,8 @@
 // that reference Gaussian j into dL/dF_j.  Layout: C/4 lanes per feature row (float4 each), 64/(C/4) rows per wave.
 #pragma once
 
-#include "common.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace mirast {
 
@@ -20,7 +21,7 @@ template <int LPR>
 __device__ __forceinline__ float row_sum(float v)
 {
 #pragma unroll
-    for (int o = 1; o < LPR; o <<= 1) v += __shfl_xor(v, o, 64);
+    for (int o = 1; o < LPR; o <<= 1) v += __shfl_xor(v, o, 64);   // (LPR lanes of a row, ascending distances: not wave.h's wave_sum)
     return v;
 }
 __device__ __forceinline__ float dot4(float4 a, float4 b) { return a.x * b.x + a.y * b.y + a.z * b.z + a.w * b.w; }

@@ -34,9 +34,10 @@
 
 #include <type_traits>
 
-#include "binning.h"
 #include "blend_bwd_shared.h"
+#include "blend_rec.h"
 #include "common.h"
+#include "wave.h"
 
 namespace mirast {
 

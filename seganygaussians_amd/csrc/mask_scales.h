@@ -15,7 +15,7 @@
 #pragma once
 
 #include "../../include/mi_mask_scales.h"
-#include "common.h"
+#include "wave.h"
 
 namespace mirast {
 
@@ -131,13 +131,6 @@ __global__ void __launch_bounds__(MS_THREADS) ms_erode_resample_kernel(int M, in
 }
 
 // ---- moments: per (mask, tile) count and f64 sums ----------------------------------------------------------------------------
-__device__ inline double ms_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // partials [M][T][MS_STATS], T = ceil(H / MS_TILE_ROWS) * Wq tiles; one 64-thread workgroup per tile
 __global__ void __launch_bounds__(64) ms_moments_kernel(int M, int H, int W, int Wq, const uint64_t* __restrict__ eroded,
                                                         const float* __restrict__ depth, double fx, double fy, int T,
@@ -170,7 +163,7 @@ __global__ void __launch_bounds__(64) ms_moments_kernel(int M, int H, int W, int
         }
     }
 #pragma unroll
-    for (int k = 0; k < MS_STATS; k++) tot[k] = ms_wave_sum(tot[k]);
+    for (int k = 0; k < MS_STATS; k++) tot[k] = wave_sum(tot[k]);
     const uint64_t valid = ms_valid_bits(W, q);
     const uint64_t all_rows = (1ull << rows) - 1ull;   // rows <= MS_TILE_ROWS < 64
     for (int m = 0; m < M; m++) {
@@ -194,7 +187,7 @@ __global__ void __launch_bounds__(64) ms_moments_kernel(int M, int H, int W, int
                 }
             }
 #pragma unroll
-            for (int k = 0; k < MS_STATS; k++) st[k] = ms_wave_sum(st[k]);
+            for (int k = 0; k < MS_STATS; k++) st[k] = wave_sum(st[k]);
         }
         double v = st[0];
 #pragma unroll

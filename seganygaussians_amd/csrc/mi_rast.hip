@@ -13,7 +13,11 @@
 #include <utility>
 #include <vector>
 
-#include "binning.h"
+// the binning stages in launch order: count (full or lean lists) -> range scan -> emit (full or lean) -> per-tile sort
+#include "bin_full.h"
+#include "bin_lean.h"
+#include "tile_ranges.h"
+#include "tile_sort.h"
 #include "blend_bwd.h"
 #include "blend_bwd_wave.h"   // (the profiling build compiles the PRODUCT kernel too: what tools/ measure is what ships; the ablation
                               // masks and rejected variants of rounds 2-5 are a record under tools/experiments/, compiled nowhere)
@@ -24,8 +28,11 @@
 #include "blend_fwd_x3.h"   // round 2's tile-batched bf16x3 forward: A/B comparisons only (MI_RAST_TILE_FWD)
 #endif
 #include "common.h"
+#include "fingerprint.h"
 #include "geometry.h"
 #include "lift.h"             // 2D-to-3D score lifting (mi_rast_lift): one front-to-back walk, one wave per half tile
+#include "xcd_runs.h"
+#include "xcd_stamp.h"        // (the profiling build's g_xcd_log is defined in this translation unit alone)
 
 using namespace mirast;
 
@@ -51,7 +58,7 @@ struct HostSync {
     hipEvent_t ev = nullptr;
     hipEvent_t ev2 = nullptr;
     bool ok = false;
-    // the words behind the R partial sums (binning.h: NR_*), as the host reads them and as the range scan addresses them
+    // the words behind the R partial sums (tile_ranges.h: NR_*), as the host reads them and as the range scan addresses them
     const int* words() const { return pinned + R_SLOTS * R_SLOT_STRIDE; }
     int* words_dev() const { return pinned_dev + R_SLOTS * R_SLOT_STRIDE; }
     bool init()
@@ -173,7 +180,7 @@ struct GeomPtrs {
     uint32_t* depth_key;
     BlendRec* index_rec;  // [P] {mean, id, radius, conic + opacity} in index order (written by the preprocess pass for visible Gaussians)
     int* cull_counter;    // one word: Gaussians culled although `prefiltered` was set
-    unsigned long long* band_bits;  // [MAX_BANDS][ceil(P / 64)]: per band of tile rows, one bit per Gaussian whose rect reaches it (binning.h)
+    unsigned long long* band_bits;  // [MAX_BANDS][ceil(P / 64)]: per band of tile rows, one bit per Gaussian whose rect reaches it (bin_lean.h)
     float* bwd_pack;  // [P,8] packed per-Gaussian field gradients (backward scratch)
 };
 struct ImgPtrs {
@@ -185,14 +192,14 @@ struct ImgPtrs {
     uint32_t* tile_cursor;
     int* num_rendered;
     uint32_t* tile_nsurv;   // per tile: blend-list entries the forward walked
-    uint32_t* run_bounds;   // [9]: the blend kernels' XCD runs of tiles (common.h: XcdRuns): from the range scan (equal counts, or equal
+    uint32_t* run_bounds;   // [9]: the blend kernels' XCD runs of tiles (xcd_runs.h: XcdRuns): from the range scan (equal counts, or equal
                             // modelled work)
-    int* words() const { return num_rendered + R_SLOTS * R_SLOT_STRIDE; }   // the words behind the R partial sums (binning.h: NR_*)
+    int* words() const { return num_rendered + R_SLOTS * R_SLOT_STRIDE; }   // the words behind the R partial sums (tile_ranges.h: NR_*)
 };
 struct BinPtrs {
     uint2* entries;      // per overlap: {depth bits, Gaussian id | quadrant mask << 28}, bucketed by tile (unsorted inside a tile)
     uint2* scratch;      // ping-pong buffer for tiles too long for the LDS sort
-    uint32_t* blend_list;  // per tile at range.x, in depth order: Gaussian id | quadrant mask << 28 (binning.h: emit_blend_list); full
+    uint32_t* blend_list;  // per tile at range.x, in depth order: Gaussian id | quadrant mask << 28 (tile_sort.h: emit_blend_list); full
                            // lists: the low 28 bits are the reference's point_list
 };
 
@@ -303,7 +310,7 @@ int check_forward_args(int P, int channels, int width, int height, const float* 
     return MI_RAST_OK;
 }
 
-// How the blend kernels' tiles are dealt to the eight XCDs (common.h, blend_fwd_wave.h: fwd_wave_item, binning.h: tile_ranges_kernel):
+// How the blend kernels' tiles are dealt to the eight XCDs (xcd_runs.h, blend_fwd_wave.h: fwd_wave_item, tile_ranges.h: tile_ranges_kernel):
 // one run of tiles per XCD, both blend kernels, boundaries from the range scan.
 // Measured in round 5 (profiles/r05_xcd_balance.md; cfg3s = density varying over the image, cfg3 = uniform): equal tile counts 447 / 844
 // views/s; this model 493 / 835 (cap 384 ... 1024, fix 32 ... 128 tried: 768 / 128 best; no cap -- the list length -- 428: a long list
@@ -347,7 +354,7 @@ struct FrontArgs {
     int* radii;
 };
 
-// How the count and emit passes walk the tile grid (binning.h)
+// How the count and emit passes walk the tile grid (bin_full.h, bin_lean.h)
 struct BinPlan {
     // FULL lists (parity tests): images with more tiles than one launch of the full count / emit passes has LDS counters for are walked
     // in bands of tile rows by the host (grid_x + 2: the count pass keeps band_rows (+ 1) rows of an odd stride >= grid_x + 1)
@@ -358,7 +365,7 @@ struct BinPlan {
     // `debug` flag or MI_RAST_FULL_LISTS -- ; otherwise only the overlaps that pass the cull are listed.
     bool nocull, full;
     // full lists: <= 256 workgroups of 1024 threads, each a slice of the Gaussians (64-index chunks dealt round robin); lean lists:
-    // workgroups dealt to the bands in proportion to the bands' Gaussian counts (binning.h: band_plan), at least one per band
+    // workgroups dealt to the bands in proportion to the bands' Gaussian counts (bin_lean.h: band_plan), at least one per band
     int nwg;
 };
 // (refuses what the passes cannot index, before any buffer is asked for or any work queued)
@@ -429,7 +436,7 @@ int opt_in_to_large_lds(int dev)
     return MI_RAST_OK;
 }
 
-// count pass over slices, scan over (tile, slice), scan over tiles -> ranges (binning.h).  R is known after the preprocess pass; the
+// count pass over slices, scan over (tile, slice), scan over tiles -> ranges (bin_full.h, tile_ranges.h; lean lists: bin_lean.h).  R is known after the preprocess pass; the
 // count pass stores its partial sums into the host's pinned buffer (event ev), and the host reads them while the scans run.
 int count_and_scan_stage(const Call& c, const BinPlan& bp, const HostSync& hs)
 {
@@ -468,7 +475,7 @@ int count_and_scan_stage(const Call& c, const BinPlan& bp, const HostSync& hs)
     return MI_RAST_OK;
 }
 
-// The emit pass: every overlap into its tile's bucket of bin.entries, unsorted (binning.h)
+// The emit pass: every overlap into its tile's bucket of bin.entries, unsorted (bin_full.h, bin_lean.h)
 int emit_stage(const Call& c, const BinPlan& bp, int R)
 {
     const int P = c.P, ntiles = (int)c.ntiles();
@@ -833,7 +840,7 @@ size_t mi_rast_image_layout(int width, int height, size_t* off)
     off[MI_IMG_N_CONTRIB] = c.take(n * sizeof(uint32_t));
     off[MI_IMG_RANGES] = c.take((tiles ? tiles : 1) * sizeof(uint2));
     off[MI_IMG_TILE_CONSUMED] = c.take((tiles ? tiles : 1) * sizeof(uint32_t));
-    // tile_count holds partial[slice][tile] of the count / emit passes (binning.h); tile_cursor the tile totals
+    // tile_count holds partial[slice][tile] of the count / emit passes (bin_full.h, bin_lean.h); tile_cursor the tile totals
     constexpr int max_slices = BIN_MAX_WG;   // (the lean passes' [workgroup][tile of its band] table is far smaller: BIN_LEAN_WG x a band's tiles)
     off[MI_IMG_TILE_COUNT] = c.take((size_t)max_slices * (tiles ? tiles : 1) * sizeof(uint32_t));
     off[MI_IMG_TILE_CURSOR] = c.take((tiles ? tiles : 1) * sizeof(uint32_t));
@@ -980,7 +987,7 @@ int mi_rast_forward_reuse(int P, int channels, int R, const float* background, i
     c.longest_run = longest_run > 0 ? std::min((uint32_t)longest_run, xcd_max_run(ntiles)) : 0u;
     {
         // the per-view words of the image buffer that the binning stages of the cached forward wrote: tile ranges, {R, longest list,
-        // key bits}, the XCD run boundaries -- copied; the per-tile walk counters of the blend kernels -- zeroed (binning.h)
+        // key bits}, the XCD run boundaries -- copied; the per-tile walk counters of the blend kernels -- zeroed (fingerprint.h)
         StageTimer t(c.stream, MI_STAGE_TILE_SCAN);
         hipLaunchKernelGGL(reuse_image_state_kernel, dim3((ntiles + 255) / 256), dim3(256), 0, c.stream, ntiles, (const uint2*)cached_ranges,
                            cached_words, c.img.ranges, c.img.words(), c.img.tile_consumed, c.img.tile_nsurv);

@@ -23,7 +23,8 @@
 #pragma once
 
 #include "../../include/mi_photometric.h"
-#include "common.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace mirast {
 
@@ -105,7 +106,7 @@ __device__ inline void ph_vertical(const float (*h)[PH_TW], int r0, int c, float
 __device__ inline double ph_block_sum(double v, double* scratch /* [PH_THREADS / 64] */)
 {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);   // (__shfl_down, lane 0 only: not wave.h's wave_sum, whose order differs)
     if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
     __syncthreads();
     double s = 0.0;

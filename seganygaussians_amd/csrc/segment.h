@@ -20,7 +20,8 @@
 #pragma once
 
 #include "../../include/mi_segment.h"
-#include "common.h"
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 
 namespace mirast {
 

@@ -18,9 +18,7 @@
 //                  of two f32 is exact there), butterfly reductions in a fixed lane order, then the logistic.
 #pragma once
 
-#include <hip/hip_runtime.h>
-
-#include <stdint.h>
+#include "wave.h"
 
 namespace mirast {
 
@@ -30,13 +28,6 @@ constexpr int VG_CHUNK = 16;       // channels per accumulation pass of the mask
 constexpr int VG_MASK_GROUP = 4;   // masks per workgroup of the mask sums
 constexpr int VG_CR_ROWS = 4;      // rows per wave of the relevancy kernel
 constexpr int VG_CR_SLOTS = 16;    // 64 lanes x 16 = 1024 = MI_VOTE_MAX_EMBED_DIM
-
-__device__ inline double vg_wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
 
 // ---- resample: Fs[c][y w + x] = bilinear sample of rendered (C, H, W), align_corners=False ---------------------------------------
 __device__ inline void vg_taps(double scale, int dst, int in_size, int& i0, int& i1, double& lam)
@@ -85,7 +76,7 @@ __global__ void __launch_bounds__(64) vg_mask_sums_kernel(int M, int C, int h, i
     const int m_end = min(M, ((int)blockIdx.y + 1) * VG_MASK_GROUP);
     for (int m = blockIdx.y * VG_MASK_GROUP; m < m_end; m++) {
         const uint64_t wd = lane < rows ? eroded[((size_t)m * h + y0 + lane) * Wq + q] : 0ull;   // lane r: the word of row y0 + r
-        const int n = (int)vg_wave_sum((double)__popcll(wd));
+        const int n = (int)wave_sum((double)__popcll(wd));
         if (lane == 0) counts[(size_t)m * T + t] = (double)n;
         if (n == 0) continue;   // wave-uniform
         const float* g = gates + (size_t)m * C;
@@ -119,7 +110,7 @@ __global__ void __launch_bounds__(64) vg_mask_sums_kernel(int M, int C, int h, i
             double mine = 0.0;
 #pragma unroll
             for (int j = 0; j < VG_CHUNK; j++) {
-                const double s = vg_wave_sum(acc[j]);
+                const double s = wave_sum(acc[j]);
                 mine = lane == j ? s : mine;
             }
             if (lane < VG_CHUNK && c0 + lane < C) sums[((size_t)m * T + t) * C + c0 + lane] = mine;
@@ -221,7 +212,7 @@ __global__ void __launch_bounds__(VG_THREADS) vg_popcount_kernel(int M, int word
     int n = 0;
     for (int i = lane; i < words; i += 64) n += __popc((unsigned)bits[(size_t)m * words + i]);
 #pragma unroll
-    for (int off = 32; off; off >>= 1) n += __shfl_xor(n, off);
+    for (int off = 32; off; off >>= 1) n += __shfl_xor(n, off);   // (not wave.h's wave_sum: the kernel's code would change)
     if (lane == 0) counts[m] = n;
 }
 
@@ -248,7 +239,7 @@ __global__ void __launch_bounds__(VG_THREADS) vg_relevancy_kernel(int N, int D, 
             e[r][i] = d < D ? (float)embeds[(size_t)n * D + d] : 0.f;
             ss = fma((double)e[r][i], (double)e[r][i], ss);
         }
-        inv[r] = normalize ? 1.0 / fmax(sqrt(vg_wave_sum(ss)), 1e-12) : 1.0;
+        inv[r] = normalize ? 1.0 / fmax(sqrt(wave_sum(ss)), 1e-12) : 1.0;
     }
     double best[VG_CR_ROWS], dot[VG_CR_ROWS];
     // the negatives first (their maximum), then one output per positive
@@ -266,7 +257,7 @@ __global__ void __launch_bounds__(VG_THREADS) vg_relevancy_kernel(int N, int D, 
         }
 #pragma unroll
         for (int r = 0; r < VG_CR_ROWS; r++) {
-            const double s = vg_wave_sum(dot[r]) * inv[r];
+            const double s = wave_sum(dot[r]) * inv[r];
             if (k < Q) {
                 best[r] = k == 0 ? s : fmax(best[r], s);
             } else if (lane == 0 && n0 + r < N) {

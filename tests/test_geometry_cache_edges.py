@@ -7,7 +7,7 @@ The reference of every case is the same Python program with the cache disabled (
 uncached path is pinned against the oracle and the reference elsewhere).  Images, masks, depths and radii must be equal bit for bit,
 every gradient within 2e-5 of the largest reference element (the order of the atomic sums).  Each render of a loss weights its
 outputs with a dL image of its own, so that wrongly shared or missing contributions cannot cancel.  Images have 70 tiles: every
-XCD run of the blend kernels has queued tiles (common.h: xcd_grab_runs).
+XCD run of the blend kernels has queued tiles (xcd_runs.h: xcd_grab_runs).
 
 The fingerprint kernel, which decides whether a cached state is reused, is checked word for word against a host restatement."""
 import ctypes as C
@@ -309,7 +309,7 @@ def test_bad_inputs_raise_as_uncached(cache, monkeypatch, bad):
     assert str(cached.value) == str(plain.value)
 
 
-# ---- the fingerprint against a host restatement of fingerprint_kernel (csrc/binning.h) -------------------------------------------
+# ---- the fingerprint against a host restatement of fingerprint_kernel (csrc/fingerprint.h) -------------------------------------------
 def _fp_ref(w):
     """sum over i of fmix32(w[i] ^ (u32(i) * 0x9E3779B1 + u32(i >> 32))) * 0x9E3779B97F4A7C15 + i, mod 2^64."""
     w = np.asarray(w, np.uint32)

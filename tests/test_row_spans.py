@@ -1,5 +1,5 @@
 """CPU property test of the row spans behind the lean lists (seganygaussians_amd/csrc/cull.h: shrink_rect, span_prepare,
-band_columns; binning.h: bin_spans_kernel).
+band_columns; bin_lean.h: bin_spans_kernel).
 
 The product default lists a (Gaussian, tile) overlap only where the closed-form column interval of one of the tile's two
 8-pixel bands says a pixel can reach alpha >= 1/255, and marks the quadrants the intervals cover.  That is only correct if

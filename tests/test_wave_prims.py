@@ -1,4 +1,4 @@
-"""The wave-level primitives the binning kernels rest on (seganygaussians_amd/csrc/binning.h), checked ON THE GPU against serial
+"""The wave-level primitives the binning kernels rest on (seganygaussians_amd/csrc/wave.h), checked ON THE GPU against serial
 restatements by tools/wave_prims_probe.hip (built by __graft_entry__.build()): the seven-DPP inclusive scan (sum and running
 maximum), wave_owner -- the owner search of the count / emit passes' balanced walks: a ballot, one LDS scatter, a DPP scan -- against
 a linear search over random item counts, and every lane_xor<M> of the wave-per-tile bitonic sorter.  Round 6's one memory fault was a

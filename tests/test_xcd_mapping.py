@@ -1,5 +1,5 @@
-"""CPU check of the blend kernels' workgroup -> (tile, quadrant) assignments (seganygaussians_amd/csrc/common.h: xcd_run_start,
-xcd_max_run, xcd_static_len_max, xcd_queued_tiles_max, xcd_clamp_runs, xcd_grab_runs; binning.h: tile_ranges_kernel's runs;
+"""CPU check of the blend kernels' workgroup -> (tile, quadrant) assignments (seganygaussians_amd/csrc/xcd_runs.h: xcd_run_start,
+xcd_max_run, xcd_static_len_max, xcd_queued_tiles_max, xcd_clamp_runs, xcd_grab_runs; tile_ranges.h: tile_ranges_kernel's runs;
 blend_bwd_wave.h: the end of the kernel; blend_fwd_wave.h: fwd_wave_item), restated in Python.
 
 Both blend kernels: the row-major tile sequence is cut into eight contiguous runs -- equal tile counts (MI_RAST_EQUAL_RUNS) or
@@ -10,7 +10,7 @@ at least one taker per queued item.
 Forward: one run per XCD; every (tile, quadrant) has exactly one id in the grid sized for the longest run."""
 import numpy as np
 
-QUEUE_DIV, MAX_RUN_FACTOR = 2, 2   # common.h
+QUEUE_DIV, MAX_RUN_FACTOR = 2, 2   # xcd_runs.h
 TILE_WEIGHT = 128                  # a tile's fixed weight (mi_rast.hip: RUN_MODEL_FIX)
 
 
@@ -31,7 +31,7 @@ def queued_tiles_max(n):
 
 
 def clamp_runs(b, n):
-    """common.h: xcd_clamp_runs."""
+    """xcd_runs.h: xcd_clamp_runs."""
     b = list(b)
     mr = max_run(n)
     b[0], b[8] = 0, n
@@ -43,7 +43,7 @@ def clamp_runs(b, n):
 
 
 def bounds_from_walks(nsurv):
-    """The equal-weight cut of the XCD runs, per-tile weight nsurv + TILE_WEIGHT, and the clamp (common.h: xcd_clamp_runs) --
+    """The equal-weight cut of the XCD runs, per-tile weight nsurv + TILE_WEIGHT, and the clamp (xcd_runs.h: xcd_clamp_runs) --
     what tile_ranges_kernel does with its modelled weights (bounds_from_model)."""
     n = len(nsurv)
     w = np.concatenate([[0], np.cumsum(np.asarray(nsurv, np.int64) + TILE_WEIGHT)])
@@ -55,7 +55,7 @@ def bounds_from_walks(nsurv):
 
 
 def bounds_from_model(counts, cap, fix):
-    """binning.h: tile_ranges_kernel with run_cap > 0: runs of equal sum(min(list length, cap) + fix)."""
+    """tile_ranges.h: tile_ranges_kernel with run_cap > 0: runs of equal sum(min(list length, cap) + fix)."""
     return bounds_from_walks(np.minimum(np.asarray(counts, np.int64), cap) + fix - TILE_WEIGHT)
 
 
@@ -138,7 +138,7 @@ def longest_of(b, n):
 
 
 def piece_search_bounds(counts, cap, fix):
-    """binning.h: tile_ranges_kernel with run_cap > 0, as the kernel does it: 1024 threads own contiguous pieces of `per` tiles, a
+    """tile_ranges.h: tile_ranges_kernel with run_cap > 0, as the kernel does it: 1024 threads own contiguous pieces of `per` tiles, a
     boundary k lies in the ONE piece whose weight prefix brackets k W / 8, and that piece's thread walks its tiles."""
     n = len(counts)
     w = np.minimum(np.asarray(counts, np.int64), cap) + fix
@@ -186,7 +186,7 @@ def test_product_forward_mapping_and_piece_search():
             assert got == list(range(4 * n)), (n, law)
 
 
-# ---- bands of the lean count / emit passes (binning.h: band_geometry, band_plan) ----------------------------------------------------
+# ---- bands of the lean count / emit passes (bin_lean.h: band_geometry, band_plan) ----------------------------------------------------
 MAX_BANDS, SPAN_MAX_HEAD_WORDS = 24, 40 * 1024 - 16 * 64 * 18 - 64
 
 

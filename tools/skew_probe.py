@@ -1,4 +1,4 @@
-"""Does the backward blend's tile scheduling (common.h: contiguous runs per XCD + queues with stealing) cope with a scene that
+"""Does the backward blend's tile scheduling (xcd_runs.h: contiguous runs per XCD + queues with stealing) cope with a scene that
 fills only part of the image?  cfg3 with all Gaussians, with a random half of them, and with the half that projects into the
 lower / right / upper-left part of the image: per-stage times and the backward's time per walked list entry.
    python tools/skew_probe.py"""

@@ -1,11 +1,11 @@
-// Checks the wave-level primitives of csrc/binning.h on the GPU against serial restatements: the seven-DPP inclusive scan (sum / max),
+// Checks the wave-level primitives of csrc/wave.h on the GPU against serial restatements: the seven-DPP inclusive scan (sum / max),
 // the scatter + max-scan owner search of the count / emit passes, and the lane exchanges of the wave-per-tile bitonic sorter.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I seganygaussians_amd/csrc tools/wave_prims_probe.hip -o tools/wave_prims_probe.bin
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "binning.h"
+#include "wave.h"
 using namespace mirast;
 
 __global__ void probe(const uint32_t* in, uint32_t* out_sum, uint32_t* out_max, uint32_t* out_xor, uint32_t* out_owner, int nbase)

@@ -38,7 +38,7 @@ pad = np.zeros((ty * 16, tx * 16), np.int64)
 pad[:H, :W] = nc
 Lq = pad.reshape(ty, 2, 8, tx, 2, 8).max(axis=(2, 5))          # [ty, qy, tx, qx]: entries the quadrant's backward walks
 nr_off = ioff["num_rendered"] + 4 * (64 * 32 + 4)
-bounds = g._view(g.img, nr_off, 9, np.uint32).astype(np.int64)   # the blend kernels' XCD runs (binning.h: NR_RUN_BOUNDS)
+bounds = g._view(g.img, nr_off, 9, np.uint32).astype(np.int64)   # the blend kernels' XCD runs (tile_ranges.h: NR_RUN_BOUNDS)
 
 # rows of every (tile, quadrant): Gaussian ids back to front
 quad_rows = [None] * (4 * nt)

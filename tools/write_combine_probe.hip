@@ -1,5 +1,5 @@
 // Does the L2 combine scattered 8-byte stores into whole lines when a workgroup's store frontier is small?
-// The emit pass of the binning (csrc/binning.h: bin_spans_kernel<true>) stores 2.9 M 8-byte entries per cfg3 view, each into a tile's
+// The emit pass of the binning (csrc/bin_lean.h: bin_spans_kernel<true>) stores 2.9 M 8-byte entries per cfg3 view, each into a tile's
 // segment at the cursor of the storing workgroup's slice: 256 slices x 8160 tiles, ~1.4 entries per (slice, tile) -- every store is
 // its own 64-byte write (WRITE_SIZE = 64 B x stores, profiles/r05_pmc.md) and the pass is bound by them (profiles/r06_front_half.md).
 // Pattern A restates that.  Pattern B gives every workgroup a BAND of tiles (16 bands x 16 sub-slices): ~22 entries per (workgroup,

@@ -1,6 +1,6 @@
 """Per-XCD finish times of the two blend kernels (is the run model's balance what the kernel times suggest?).
 PROFILING library only (MI_RAST_LIB=seganygaussians_amd/libmi_rast_prof.so): every wave of blend_fwd_wave_kernel / blend_bwd_wave_kernel
-stores the 100-MHz clock at its start and end into its own two words (csrc/common.h: MI_XCD_STAMP); per XCD the earliest start and the
+stores the 100-MHz clock at its start and end into its own two words (csrc/xcd_stamp.h: MI_XCD_STAMP); per XCD the earliest start and the
 latest end are reported.
     MI_RAST_LIB=$PWD/seganygaussians_amd/libmi_rast_prof.so python tools/xcd_stamps.py cfg3 cfg3s"""
 import ctypes as C
