@@ -22,6 +22,10 @@ def install_dropin(fuse_smoothing: bool = False, fuse_training_step: bool = Fals
     (scene/gaussian_model_ff.py:338-364) to the fused HIP gather kernels (knn_smooth.py, include/mi_knn_smooth.h): at once
     if `scene.gaussian_model_ff` is already imported, otherwise right after it is imported.  Same signature, same column
     draw from the CPU generator, same values and gradients; the reference's own PyTorch expression is no longer executed.
+    `FeatureGaussianModel.get_multi_resolution_smoothed_point_features` (:366-400, the renderer's smooth_type='multi_res') is
+    rebound with it: same state and subset draws, gradients for the features and for `smooth_weights`; outside the fused
+    kernels' limits (more than 4 levels, sum(Ks) > 32, a subset smaller than its K, a width other than 32 / 64) the
+    reference's own method runs.
 
     fuse_training_step=True (opt-in) patches `scene.gaussian_model.GaussianModel` in the same manner (training_step.py, DESIGN.md
     section 18): `training_setup` swaps the optimizer it built for a FusedAdam over the same groups, and
@@ -54,13 +58,18 @@ def _patch_now_or_on_import(module_name: str, class_name: str, patch) -> None:
 
 
 def patch_feature_model(cls) -> None:
-    """Rebinds cls.get_smoothed_point_features (the reference's FeatureGaussianModel) to the fused HIP path; idempotent.
-    The original stays reachable as cls._reference_get_smoothed_point_features."""
+    """Rebinds cls.get_smoothed_point_features and, where the class has one, cls.get_multi_resolution_smoothed_point_features
+    (the reference's FeatureGaussianModel) to the fused HIP paths; idempotent.  The originals stay reachable as
+    cls._reference_get_smoothed_point_features and cls._reference_get_multi_resolution_smoothed_point_features."""
     if getattr(cls, "_mi_fused_smoothing", False):
         return
-    from .knn_smooth import fused_get_smoothed_point_features
+    from .knn_smooth import fused_get_multi_resolution_smoothed_point_features, fused_get_smoothed_point_features
     cls._reference_get_smoothed_point_features = cls.get_smoothed_point_features
     cls.get_smoothed_point_features = fused_get_smoothed_point_features
+    multi_res = getattr(cls, "get_multi_resolution_smoothed_point_features", None)
+    if multi_res is not None and multi_res is not fused_get_multi_resolution_smoothed_point_features:
+        cls._reference_get_multi_resolution_smoothed_point_features = cls.get_multi_resolution_smoothed_point_features
+        cls.get_multi_resolution_smoothed_point_features = fused_get_multi_resolution_smoothed_point_features
     cls._mi_fused_smoothing = True
 
 

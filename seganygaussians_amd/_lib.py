@@ -32,7 +32,7 @@ EXPORTS = [
     "mi_rast_mask_backward", "mi_rast_last_error", "mi_rast_version", "mi_rast_supported_channels",
     "mi_rast_get_higher_msb", "mi_rast_geometry_layout", "mi_rast_image_layout", "mi_rast_binning_layout",
     "mi_rast_profile_enable", "mi_rast_profile_read",
-    "mi_knn_smooth_forward", "mi_knn_smooth_backward",  # include/mi_knn_smooth.h
+    "mi_knn_smooth_forward", "mi_knn_smooth_backward", "mi_knn_smooth_multi_forward", "mi_knn_smooth_multi_backward",  # include/mi_knn_smooth.h
     "mi_knn_workspace_bytes", "mi_knn_build", "mi_knn_query", "mi_knn_mean_dist2",  # include/mi_knn.h
     "mi_contrastive_forward", "mi_contrastive_backward",  # include/mi_contrastive.h
     "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
@@ -128,6 +128,10 @@ def load():
     L.mi_knn_smooth_forward.argtypes = [i, i, i, vp, u32, vp, vp, i, vp]
     L.mi_knn_smooth_backward.restype = i
     L.mi_knn_smooth_backward.argtypes = [i, i, i, vp, vp, vp, u32, vp, vp, vp, vp, i, vp]
+    L.mi_knn_smooth_multi_forward.restype = i
+    L.mi_knn_smooth_multi_forward.argtypes = [i, i, i, C.POINTER(i), vp, vp, i, vp, vp, i, vp]
+    L.mi_knn_smooth_multi_backward.restype = i
+    L.mi_knn_smooth_multi_backward.argtypes = [i, i, i, C.POINTER(i), vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, vp]
     L.mi_knn_workspace_bytes.restype = C.c_size_t
     L.mi_knn_workspace_bytes.argtypes = [i]
     L.mi_knn_build.restype = i
