@@ -38,7 +38,11 @@ EXPORTS = [
     "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
     "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
 ] + CLUSTER_EXPORTS + LIFT_EXPORTS + VOTE_GRAPH_EXPORTS
-MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_erode_min_sum", "mi_mask_scales"]   # include/mi_mask_scales.h
+# include/mi_mask_scales.h, its mask-sets section (csrc/mi_mask_sets.hip); listed on its own and as the tail of MASK_SCALES_EXPORTS
+MASK_SETS_EXPORTS = ["mi_mask_overlaps", "mi_mask_boxes", "mi_mask_nms_keep", "mi_mask_score_images"]
+MI_MASK_SCORE_MODE = {"sum": 0, "mean": 1, "max": 2}
+MI_MASK_SCORE_MAX_COLUMNS = 64
+MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_erode_min_sum", "mi_mask_scales"] + MASK_SETS_EXPORTS   # include/mi_mask_scales.h
 MI_VOTE_MAX_ANCHORS, MI_VOTE_MAX_EMBED_DIM, MI_VOTE_MAX_PROMPTS = 32768, 1024, 16
 SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
@@ -162,6 +166,14 @@ def load():
     L.mi_mask_erode_min_sum.argtypes = [i, i, i, vp, i, i, f, vp, vp]
     L.mi_mask_scales.restype = i
     L.mi_mask_scales.argtypes = [i, i, i, vp, vp, C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp]
+    L.mi_mask_overlaps.restype = i
+    L.mi_mask_overlaps.argtypes = [i, i, i, vp, vp, vp, vp, vp]
+    L.mi_mask_boxes.restype = i
+    L.mi_mask_boxes.argtypes = [i, i, i, vp, vp, vp, vp]
+    L.mi_mask_nms_keep.restype = i
+    L.mi_mask_nms_keep.argtypes = [i, vp, vp, vp, f, f, f, vp, vp]
+    L.mi_mask_score_images.restype = i
+    L.mi_mask_score_images.argtypes = [i, i, i, i, vp, vp, i, vp, vp]
     L.mi_segment_scores.restype = i
     L.mi_segment_scores.argtypes = [i, i, i, i, vp, vp, vp, i, i, vp, vp]
     L.mi_segment_select.restype = i

@@ -1,0 +1,205 @@
+"""Set operations on SAM masks on the MI355X: pairwise overlaps, boxes, mask NMS and score images.
+
+The 2-D side of the open-vocabulary path between the two networks.  The reference decides which SAM masks exist with a Python double
+loop over all mask pairs (clip_utils/sam_utils.py:123-202, mask_nms / masks_update) and paints per-mask CLIP scores into per-view
+score images by multiplying an (M, H, W) float tensor of masks (clip_utils/__init__.py:206, :282, :380).  Here the masks stay
+bit-packed on the device, in the PackedSamMasks layout (pack_sam_masks), and nothing of size (M, H, W) is formed:
+
+  * mask_overlaps()     -- AND + popcount over all pairs, tiled like a GEMM; read through an optional order.
+  * masks_to_boxes()    -- torchvision.ops.masks_to_boxes in one pass over the words; NaN rows for empty masks.
+  * mask_nms()          -- sam_utils.py:138-187: torch.sort, the overlaps through the order, one decision launch, idx[keep].
+  * masks_update()      -- sam_utils.py:189-202 for SAM's lists of dicts.
+  * mask_score_images() -- the masked sum / mean / max of per-mask scores per pixel, the input of lift_scores / vote_3d_mask.
+
+Limits, refused with ValueError before any launch: 1 <= M <= 1024, h * w < 2^24 (every pixel count is exact as a float32),
+1 <= K <= 64 score columns, float32 tensors on one GPU.  No autograd."""
+from __future__ import annotations
+
+import torch
+
+from . import _lib
+from ._ffi import check, stream_ptr
+from .contrastive_loss import MAX_MASKS, PackedSamMasks
+from .mask_scales import _as_packed
+
+MAX_PIXELS = 1 << 24
+MAX_SCORE_COLUMNS = _lib.MI_MASK_SCORE_MAX_COLUMNS
+
+
+def _f32(t, name: str, who: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    return t
+
+
+def _check_shape(masks, who: str):
+    """The limits that need no device, before anything is packed or launched (the rest is _as_packed's)."""
+    if not isinstance(masks, PackedSamMasks) and not (isinstance(masks, torch.Tensor) and masks.dtype == torch.bool and masks.dim() == 3):
+        raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got "
+                         f"{getattr(masks, 'dtype', type(masks))} {tuple(getattr(masks, 'shape', ()))}")
+    M, h, w = (int(v) for v in masks.shape)
+    if not 1 <= M <= MAX_MASKS:
+        raise ValueError(f"{who}: need 1 <= M <= {MAX_MASKS} masks, got {M}")
+    if h * w >= MAX_PIXELS:
+        raise ValueError(f"{who}: need h * w < 2^24 pixels, got {h} x {w}")
+
+
+def _packed(masks, scores, who: str) -> PackedSamMasks:
+    """masks as a PackedSamMasks on the GPU of `scores` (None: on their own GPU, or the current one for CPU masks)."""
+    _check_shape(masks, who)
+    dev = None
+    if scores is not None:
+        if not scores.is_cuda:
+            raise ValueError(f"{who}: scores must be on a GPU, got {scores.device}")
+        dev = scores.device
+    try:
+        return _as_packed(masks, dev, who)
+    except ValueError as e:
+        # _as_packed words its device mismatch for sam_mask_scales' depth
+        raise ValueError(str(e).replace("the depth on", "the scores on")) from None
+
+
+def _overlaps(packed: PackedSamMasks, order):
+    M, h, w = packed.shape
+    dev = packed.device
+    inter = torch.empty((M, M), device=dev, dtype=torch.int32)
+    areas = torch.empty((M,), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        check(_lib.load().mi_mask_overlaps(M, h, w, packed.words.data_ptr(), None if order is None else order.data_ptr(),
+                                           inter.data_ptr(), areas.data_ptr(), stream_ptr(dev)))
+    return inter, areas
+
+
+def mask_overlaps(masks, order=None):
+    """The pairwise intersections of M masks: (inter, areas).
+
+    masks: bool (M, h, w) on the CPU or a GPU (packed here), or a PackedSamMasks.  order: optional (M,) int64 permutation of
+    0 .. M-1 on the masks' GPU; the masks are read through it and never copied (checked here, at the cost of one synchronisation).
+    inter: (M, M) int32, inter[a, b] = the number of pixels in both mask order[a] and mask order[b]; symmetric, the areas on its
+    diagonal.  areas: (M,) int64 in the same order.  Exact."""
+    packed = _packed(masks, None, "mask_overlaps")
+    M = packed.shape[0]
+    if order is not None:
+        if not isinstance(order, torch.Tensor) or order.dtype != torch.int64 or tuple(order.shape) != (M,):
+            raise ValueError(f"mask_overlaps: order must be an int64 ({M},) tensor, got "
+                             f"{getattr(order, 'dtype', type(order))} {tuple(getattr(order, 'shape', ()))}")
+        if order.device != packed.device:
+            raise ValueError(f"mask_overlaps: the masks are on {packed.device}, the order on {order.device}")
+        order = order.contiguous()
+        if not torch.equal(torch.sort(order).values, torch.arange(M, device=order.device)):
+            raise ValueError("mask_overlaps: order must be a permutation of 0 .. M-1")
+    return _overlaps(packed, order)
+
+
+def masks_to_boxes(masks, return_areas: bool = False):
+    """torchvision.ops.masks_to_boxes (clip_utils/__init__.py:115) on packed masks: (M, 4) float32 rows (x_min, y_min, x_max, y_max)
+    of the set pixels, inclusive.  A mask with no pixel gets a NaN row (torchvision raises there; sam_mask_scales answers NaN for
+    degenerate masks too).  With return_areas, also the pixel counts (M,) int64."""
+    packed = _packed(masks, None, "masks_to_boxes")
+    M, h, w = packed.shape
+    dev = packed.device
+    boxes = torch.empty((M, 4), device=dev, dtype=torch.float32)
+    areas = torch.empty((M,), device=dev, dtype=torch.int64) if return_areas else None
+    with torch.cuda.device(dev):
+        check(_lib.load().mi_mask_boxes(M, h, w, packed.words.data_ptr(), boxes.data_ptr(),
+                                        None if areas is None else areas.data_ptr(), stream_ptr(dev)))
+    return (boxes, areas) if return_areas else boxes
+
+
+def _threshold(v, name: str) -> float:
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        raise ValueError(f"mask_nms: {name} must be a number, got {v!r}") from None
+    if v != v:
+        raise ValueError(f"mask_nms: {name} is NaN")
+    return v
+
+
+def mask_nms(masks, scores, iou_thr=0.7, score_thr=0.1, inner_thr=0.2, **kwargs):
+    """clip_utils/sam_utils.py:123-187: mask non-maximum suppression.  Returns selected_idx (int64, on the scores' GPU), the kept
+    masks in descending-score order, like the reference's idx[keep].
+
+    masks: bool (M, h, w) on the CPU or the scores' GPU, or a PackedSamMasks there; scores: (M,) float32 on a GPU.  Extra keyword
+    arguments are ignored, as in the reference.  torch.sort on the device, the overlap kernel through the sort's indices, one
+    decision launch, idx[keep]; no (M, M) matrix reaches the host.  The decision is the reference's float32 arithmetic operation
+    for operation (include/mi_mask_scales.h states it), its quirks included: the lower inner test also sees the pair (c-1, c)
+    (torch.tril(..., diagonal=1) at :164), and of two empty masks the lower-scored one is dropped (0/0 union).
+
+    Where this differs from the reference:
+      * the fallbacks (:173-181).  When no score passes score_thr, or every upper inner test fails, or every lower inner test
+        fails, the reference means to switch that one test on for the three best-scored masks, but its keep_conf[index, 0] raises
+        IndexError on the 1-D tensor it has (RuntimeError for M < 3).  Here the intent is built: that test is set true for the
+        first min(3, M) masks of the sorted order.
+      * ties in `scores` are ordered by a stable sort; the reference's order is unspecified there."""
+    scores = _f32(scores, "scores", "mask_nms")
+    iou_thr, score_thr = _threshold(iou_thr, "iou_thr"), _threshold(score_thr, "score_thr")
+    inner_max = 1.0 - _threshold(inner_thr, "inner_thr")   # :169-170 subtract in Python doubles; the comparison is in float32
+    packed = _packed(masks, scores, "mask_nms")
+    M, dev = packed.shape[0], scores.device
+    if tuple(scores.shape) != (M,):
+        raise ValueError(f"mask_nms: scores must be ({M},) for {M} masks, got {tuple(scores.shape)}")
+    s, idx = torch.sort(scores.detach(), dim=0, descending=True, stable=True)
+    inter, areas = _overlaps(packed, idx)
+    keep = torch.empty((M,), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        check(_lib.load().mi_mask_nms_keep(M, inter.data_ptr(), areas.data_ptr(), s.data_ptr(), iou_thr, score_thr, inner_max,
+                                           keep.data_ptr(), stream_ptr(dev)))
+    return idx[keep.bool()]
+
+
+def masks_update(*levels, **kwargs):
+    """clip_utils/sam_utils.py:189-202: removes redundant masks from each of SAM's mask lists (lists of dicts with 'segmentation',
+    'predicted_iou', 'stability_score'), by mask_nms with scores = stability_score * predicted_iou (in float32).  Returns a tuple
+    of the filtered lists, each in its original order; the keyword arguments go to mask_nms.  Runs on the current GPU.  An empty
+    list stays empty."""
+    import numpy as np
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = ()
+    for lvl in levels:
+        if len(lvl) == 0:
+            out += ([],)
+            continue
+        seg = torch.from_numpy(np.stack([np.asarray(m["segmentation"], dtype=bool) for m in lvl], axis=0))
+        iou_pred = np.stack([m["predicted_iou"] for m in lvl], axis=0)
+        stability = np.stack([m["stability_score"] for m in lvl], axis=0)
+        scores = torch.as_tensor(stability * iou_pred, dtype=torch.float32).to(dev)
+        kept = set(mask_nms(seg.to(dev), scores, **kwargs).tolist())
+        out += ([m for i, m in enumerate(lvl) if i in kept],)
+    return out
+
+
+def mask_score_images(scores, masks, mode: str = "mean", out=None):
+    """Per-mask scores painted into score images: (K, h, w) float32, the input of lift_scores / vote_3d_mask as it is.
+
+    scores: (M,) or (M, K) float32 on a GPU, finite (clip_relevancy's result); masks: bool (M, h, w) on the CPU or the scores'
+    GPU, or a PackedSamMasks there.  Per pixel p and column k, over the masks m that cover p, in ascending m, with a float32
+    accumulator:
+      "sum"  : the sum of scores[m, k]                                          (get_multi_lvl_scores, clip_utils/__init__.py:380)
+      "mean" : that sum / the number of covering masks, 0 where none covers p    (get_segmentation, :282: in float32 count + 1e-9
+               is count, and 0 / 1e-9 is 0)
+      "max"  : max over all M masks of scores[m, k] * bit_m(p): a mask that does not cover p contributes 0   (get_scores, :206)
+    out: an optional contiguous float32 (K, h, w) tensor on that GPU to write into.  Deterministic: no atomics."""
+    scores = _f32(scores, "scores", "mask_score_images")
+    if mode not in _lib.MI_MASK_SCORE_MODE:
+        raise ValueError(f"mask_score_images: mode must be one of {sorted(_lib.MI_MASK_SCORE_MODE)}, got {mode!r}")
+    if scores.dim() not in (1, 2):
+        raise ValueError(f"mask_score_images: scores must be (M,) or (M, K), got {tuple(scores.shape)}")
+    K = 1 if scores.dim() == 1 else int(scores.shape[1])
+    if not 1 <= K <= MAX_SCORE_COLUMNS:
+        raise ValueError(f"mask_score_images: need 1 <= K <= {MAX_SCORE_COLUMNS} score columns, got {K}")
+    packed = _packed(masks, scores, "mask_score_images")
+    M, h, w = packed.shape
+    dev = scores.device
+    if int(scores.shape[0]) != M:
+        raise ValueError(f"mask_score_images: {int(scores.shape[0])} score rows for {M} masks")
+    if out is None:
+        out = torch.empty((K, h, w), device=dev, dtype=torch.float32)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (K, h, w) or out.dtype != torch.float32 or out.device != dev \
+            or not out.is_contiguous():
+        raise ValueError(f"mask_score_images: out must be a contiguous float32 ({K}, {h}, {w}) tensor on {dev}")
+    s = scores.detach().contiguous()
+    with torch.cuda.device(dev):
+        check(_lib.load().mi_mask_score_images(M, h, w, K, packed.words.data_ptr(), s.data_ptr(), _lib.MI_MASK_SCORE_MODE[mode],
+                                               out.data_ptr(), stream_ptr(dev)))
+    return out
