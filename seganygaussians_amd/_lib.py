@@ -42,7 +42,11 @@ EXPORTS = [
 MASK_SETS_EXPORTS = ["mi_mask_overlaps", "mi_mask_boxes", "mi_mask_nms_keep", "mi_mask_score_images"]
 MI_MASK_SCORE_MODE = {"sum": 0, "mean": 1, "max": 2}
 MI_MASK_SCORE_MAX_COLUMNS = 64
-MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_erode_min_sum", "mi_mask_scales"] + MASK_SETS_EXPORTS   # include/mi_mask_scales.h
+# include/mi_mask_scales.h, its CLIP-tiles section (csrc/mi_clip_tiles.hip; mi_mask_resize in csrc/mi_mask_scales.hip)
+CLIP_TILES_EXPORTS = ["mi_mask_resize", "mi_mask_clip_tiles", "mi_mask_index_map"]
+MI_CLIP_TILES_LAYOUT = {"crop": 0, "pad_square": 1}
+MI_CLIP_TILES_MAX_SIZE, MI_CLIP_TILES_MAX_SIDE = 512, 32768
+MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_erode_min_sum", "mi_mask_scales"] + MASK_SETS_EXPORTS + CLIP_TILES_EXPORTS   # include/mi_mask_scales.h
 MI_VOTE_MAX_ANCHORS, MI_VOTE_MAX_EMBED_DIM, MI_VOTE_MAX_PROMPTS = 32768, 1024, 16
 SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
 MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
@@ -174,6 +178,12 @@ def load():
     L.mi_mask_nms_keep.argtypes = [i, vp, vp, vp, f, f, f, vp, vp]
     L.mi_mask_score_images.restype = i
     L.mi_mask_score_images.argtypes = [i, i, i, i, vp, vp, i, vp, vp]
+    L.mi_mask_resize.restype = i
+    L.mi_mask_resize.argtypes = [i, i, i, vp, i, i, f, vp, vp]
+    L.mi_mask_clip_tiles.restype = i
+    L.mi_mask_clip_tiles.argtypes = [i, i, i, vp, vp, vp, i, f, i, C.POINTER(f), C.POINTER(f), i, i, i, vp, vp]
+    L.mi_mask_index_map.restype = i
+    L.mi_mask_index_map.argtypes = [i, i, i, vp, i, vp, vp]
     L.mi_segment_scores.restype = i
     L.mi_segment_scores.argtypes = [i, i, i, i, vp, vp, vp, i, i, vp, vp]
     L.mi_segment_select.restype = i

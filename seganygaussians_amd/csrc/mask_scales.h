@@ -8,6 +8,7 @@
 //   erode (resampled) : one wave per output word, one lane per pixel.  Each of the 9 window values is PyTorch's CPU bilinear
 //                       interpolation of 4 source bits (upsample_bilinear2d, align_corners=False), summed in f32 in row-major order;
 //                       __ballot packs the 64 results.
+//   resize            : one wave per output word: the resampled value of the pixel itself > threshold (mi_mask_resize).
 //   moments           : one wave per tile of MS_TILE_ROWS rows x 64 pixels.  Each lane holds its pixels' points (f64), the wave
 //                       loops over the masks and writes, per mask, the tile's count and sums of x, y, z and |p|^2 (f64).  Tiles a
 //                       mask misses cost one ballot; tiles it covers use the tile totals.
@@ -127,6 +128,35 @@ __global__ void __launch_bounds__(MS_THREADS) ms_erode_resample_kernel(int M, in
         }
     }
     const uint64_t word = __ballot(x < W && box >= min_sum);
+    if (lane == 0) out[i] = word;
+}
+
+// ---- resize: the resampled value alone, against a threshold (clip_utils/__init__.py:99-102) -----------------------------------
+// One wave per output word, one lane per pixel, the same taps and the same rounding order as the window values above.
+__global__ void __launch_bounds__(MS_THREADS) ms_resize_kernel(int M, int h, int w, int Wqi, const uint64_t* __restrict__ in, int H,
+                                                               int W, int Wq, float scale_h, float scale_w, float threshold,
+                                                               uint64_t* __restrict__ out)
+{
+    const size_t i = (size_t)blockIdx.x * (MS_THREADS / 64) + (threadIdx.x >> 6);   // one wave per output word
+    if (i >= (size_t)M * H * Wq) return;                                             // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int q = (int)(i % Wq);
+    const size_t mrow = i / Wq;
+    const int y = (int)(mrow % H), m = (int)(mrow / H);
+    const int x = 64 * q + lane;
+    bool bit = false;
+    if (x < W) {
+        int sy0, sy1, sx0, sx1;
+        float wy0, wy1, wx0, wx1;
+        ms_source_taps(scale_h, y, h, sy0, sy1, wy0, wy1);
+        ms_source_taps(scale_w, x, w, sx0, sx1, wx0, wx1);
+        const uint64_t* r0 = in + ((size_t)m * h + sy0) * Wqi;
+        const uint64_t* r1 = in + ((size_t)m * h + sy1) * Wqi;
+        const float t0 = ms_bit(r0, sx0) * wx0 + ms_bit(r0, sx1) * wx1;
+        const float t1 = ms_bit(r1, sx0) * wx0 + ms_bit(r1, sx1) * wx1;
+        bit = fmaf(t0, wy0, t1 * wy1) > threshold;
+    }
+    const uint64_t word = __ballot(bit);
     if (lane == 0) out[i] = word;
 }
 

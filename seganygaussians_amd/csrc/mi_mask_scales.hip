@@ -59,6 +59,28 @@ int mi_mask_erode(int M, int h, int w, const unsigned long long* packed_in, int 
     return mi_mask_erode_min_sum(M, h, w, packed_in, H, W, 5.f, packed_out, stream);
 }
 
+int mi_mask_resize(int M, int h, int w, const unsigned long long* packed_in, int H, int W, float threshold,
+                   unsigned long long* packed_out, void* stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = ms_check(M, h, w, "h, w")) return rc;
+    if (int rc = ms_check(M, H, W, "H, W")) return rc;
+    if ((size_t)h * (size_t)w >= ((size_t)1 << 24) || (size_t)H * (size_t)W >= ((size_t)1 << 24))
+        return fail(MI_RAST_ERR_INVALID, "mask resize: need h * w and H * W < 2^24 pixels");
+    if (!packed_in || !packed_out) return fail(MI_RAST_ERR_INVALID, "mask scales: null pointer");
+    if (!(threshold == threshold)) return fail(MI_RAST_ERR_INVALID, "mask resize: threshold is NaN");
+    const int Wqi = (w + 63) / 64, Wq = (W + 63) / 64;
+    const size_t in_words = (size_t)M * h * Wqi, words = (size_t)M * H * Wq;
+    if (packed_out < packed_in + in_words && packed_in < packed_out + words)
+        return fail(MI_RAST_ERR_INVALID, "mask resize: the resized masks must not overlap the input masks");
+    const float scale_h = (float)h / (float)H, scale_w = (float)w / (float)W;   // as in mi_mask_erode_min_sum
+    constexpr int wpb = MS_THREADS / 64;
+    hipLaunchKernelGGL(ms_resize_kernel, dim3((unsigned)((words + wpb - 1) / wpb)), dim3(MS_THREADS), 0, stream, M, h, w, Wqi,
+                       (const uint64_t*)packed_in, H, W, Wq, scale_h, scale_w, threshold, (uint64_t*)packed_out);
+    HIP_TRY(hipGetLastError());
+    return MI_RAST_OK;
+}
+
 int mi_mask_scales(int M, int H, int W, const unsigned long long* eroded, const float* depth, double fx, double fy, void* workspace,
                    size_t workspace_bytes, float* scales, long long* counts, void* stream_)
 {

@@ -10,6 +10,9 @@ bit-packed on the device, in the PackedSamMasks layout (pack_sam_masks), and not
   * mask_nms()          -- sam_utils.py:138-187: torch.sort, the overlaps through the order, one decision launch, idx[keep].
   * masks_update()      -- sam_utils.py:189-202 for SAM's lists of dicts.
   * mask_score_images() -- the masked sum / mean / max of per-mask scores per pixel, the input of lift_scores / vote_3d_mask.
+  * resize_sam_masks()  -- F.interpolate(masks.float(), size, mode='bilinear') > threshold (clip_utils/__init__.py:99-102), packed
+                           to packed; the masks at the image's size that clip_tiles.clip_tiles() wants.
+  * mask_index_map()    -- the per-pixel index of the last mask that covers it, -1 where none does (sam_utils.py:214, :221).
 
 Limits, refused with ValueError before any launch: 1 <= M <= 1024, h * w < 2^24 (every pixel count is exact as a float32),
 1 <= K <= 64 score columns, float32 tensors on one GPU.  No autograd."""
@@ -20,7 +23,7 @@ import torch
 from . import _lib
 from ._ffi import check, stream_ptr
 from .contrastive_loss import MAX_MASKS, PackedSamMasks
-from .mask_scales import _as_packed
+from .mask_scales import _as_packed, _size
 
 MAX_PIXELS = 1 << 24
 MAX_SCORE_COLUMNS = _lib.MI_MASK_SCORE_MAX_COLUMNS
@@ -202,4 +205,52 @@ def mask_score_images(scores, masks, mode: str = "mean", out=None):
     with torch.cuda.device(dev):
         check(_lib.load().mi_mask_score_images(M, h, w, K, packed.words.data_ptr(), s.data_ptr(), _lib.MI_MASK_SCORE_MODE[mode],
                                                out.data_ptr(), stream_ptr(dev)))
+    return out
+
+
+def resize_sam_masks(masks, size, threshold=0.5) -> PackedSamMasks:
+    """clip_utils/__init__.py:99-102: the masks at another size.  Bit (y, x) of the result is
+    F.interpolate(masks.float(), size, mode='bilinear')[m, y, x] > threshold, the value being PyTorch's CPU bilinear of four source
+    bits, bit for bit (the taps and the rounding order of erode_sam_masks' resampled branch).
+
+    masks: bool (M, h, w) on the CPU or a GPU (packed here), or a PackedSamMasks; size: (H, W) with H * W < 2^24.  Returns a
+    PackedSamMasks (M, H, ceil(W / 64)) on the masks' GPU (the current one for CPU masks), padding bits 0.  At the same size the
+    value is the bit itself, so the result is a copy for 0 <= threshold < 1.  One launch."""
+    H, W = _size(size, "resize_sam_masks")
+    if H * W >= MAX_PIXELS:
+        raise ValueError(f"resize_sam_masks: need H * W < 2^24 pixels, got {H} x {W}")
+    try:
+        threshold = float(threshold)
+    except (TypeError, ValueError):
+        raise ValueError(f"resize_sam_masks: threshold must be a number, got {threshold!r}") from None
+    if threshold != threshold:
+        raise ValueError("resize_sam_masks: threshold is NaN")
+    packed = _packed(masks, None, "resize_sam_masks")
+    M, h, w = packed.shape
+    dev = packed.device
+    out = torch.empty((M, H, (W + 63) // 64), device=dev, dtype=torch.int64)
+    with torch.cuda.device(dev):
+        check(_lib.load().mi_mask_resize(M, h, w, packed.words.data_ptr(), H, W, threshold, out.data_ptr(), stream_ptr(dev)))
+    return PackedSamMasks(out, (M, H, W))
+
+
+def mask_index_map(masks, offset: int = 0, out=None) -> torch.Tensor:
+    """The seg_map of clip_utils/sam_utils.py:214 and :221 (mask2segmap): (h, w) int32, per pixel `offset` + the highest index of
+    a mask that covers it -- the reference paints the masks in ascending order, so the last one stays -- and -1, without the offset,
+    where no mask covers the pixel (:62 adds the cumulated lengths of the earlier levels to every value but -1).
+
+    masks: bool (M, h, w) on the CPU or a GPU, or a PackedSamMasks; 0 <= offset <= 2^31 - 1025; out: an optional contiguous int32
+    (h, w) tensor on the masks' GPU to write into.  One launch that reads the mask words once.  Exact."""
+    if isinstance(offset, bool) or not isinstance(offset, int) or not 0 <= offset <= (1 << 31) - 1 - MAX_MASKS:
+        raise ValueError(f"mask_index_map: offset must be an int in 0 .. 2^31 - 1 - {MAX_MASKS}, got {offset!r}")
+    packed = _packed(masks, None, "mask_index_map")
+    M, h, w = packed.shape
+    dev = packed.device
+    if out is None:
+        out = torch.empty((h, w), device=dev, dtype=torch.int32)
+    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (h, w) or out.dtype != torch.int32 or out.device != dev \
+            or not out.is_contiguous():
+        raise ValueError(f"mask_index_map: out must be a contiguous int32 ({h}, {w}) tensor on {dev}")
+    with torch.cuda.device(dev):
+        check(_lib.load().mi_mask_index_map(M, h, w, packed.words.data_ptr(), offset, out.data_ptr(), stream_ptr(dev)))
     return out
