@@ -39,7 +39,7 @@ int mi_knn_smooth_multi_forward(int P, int C, int L, const int* level_k /* host 
                                 float* out /* [P,C] */, int normalize_out, void* stream);
 
 /* inv_offsets[P+1] / inv_entries[P*Ktot]: the inverse lists of knn_idx, as for mi_knn_smooth_backward; a list may be of any
- * length (a level whose subset has k_l members puts all P rows into k_l lists) and is summed in its stored order.
+ * length (a level whose subset has k_l members puts all P rows into k_l lists) and is summed in its stored order, with a compensated sum.
  * dret: scratch [P,C].  dL_dfeatures is overwritten (not accumulated).  dL_dweights: [P, L] (ALSO when weights_broadcast: the
  * caller sums the rows), overwritten; NULL = not wanted. */
 int mi_knn_smooth_multi_backward(int P, int C, int L, const int* level_k, const int* knn_idx, const int* inv_offsets,

@@ -272,6 +272,17 @@ __global__ void __launch_bounds__(256) knn_smooth_multi_bwd_ret_kernel(int P, in
 
 // Backward pass B: dL/dF_j from the dL/dret rows of the Gaussians i that reach j, each scaled by w[i, level] / k_level of the
 // column it reaches j through.  One lane group walks the whole list of j, whatever its length, in list order.
+// The sum is compensated (Kahan): a list may hold the same addend many times over (a cloud of one point, a subset smaller than
+// its k whose members the map repeats), every step of a plain running sum then rounds the same way, and the error grows with the
+// list's length: 8 * 2^-24 of the summed terms after 24 entries, where the reference expression in float32 stays below 2.
+__device__ __forceinline__ void kahan_add(float& sum, float& comp, float term)
+{
+    const float y = term - comp;
+    const float t = sum + y;
+    comp = (t - sum) - y;
+    sum = t;
+}
+
 template <int C>
 __global__ void __launch_bounds__(256) knn_smooth_multi_bwd_feat_kernel(int P, const int* __restrict__ inv_offsets,
                                                                         const uint32_t* __restrict__ inv_entries, SmoothLevels lv,
@@ -284,7 +295,7 @@ __global__ void __launch_bounds__(256) knn_smooth_multi_bwd_feat_kernel(int P, c
     const int gid = blockIdx.x * 256 + threadIdx.x;
     const int row = gid / LPR, part = gid % LPR;
     if (row >= P) return;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f), comp = make_float4(0.f, 0.f, 0.f, 0.f);
     const int e0 = inv_offsets[row], e1 = inv_offsets[row + 1];
     for (int e = e0; e < e1; e++) {
         const uint32_t ent = inv_entries[e];
@@ -300,10 +311,10 @@ __global__ void __launch_bounds__(256) knn_smooth_multi_bwd_feat_kernel(int P, c
         }
         coef *= level_weight(w, w_stride, i, l);
         const float4 d = reinterpret_cast<const float4*>(dret)[(size_t)i * LPR + part];
-        s.x += coef * d.x;
-        s.y += coef * d.y;
-        s.z += coef * d.z;
-        s.w += coef * d.w;
+        kahan_add(s.x, comp.x, coef * d.x);
+        kahan_add(s.y, comp.y, coef * d.y);
+        kahan_add(s.z, comp.z, coef * d.z);
+        kahan_add(s.w, comp.w, coef * d.w);
     }
     // n = F / max(|F|, eps):  dF = (s - n (n . s)) / |F|   (|F| >= eps);   dF = s / eps   (|F| < eps: n = F / eps)
     const float4 f = reinterpret_cast<const float4*>(F)[(size_t)row * LPR + part];

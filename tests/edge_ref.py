@@ -1,6 +1,6 @@
-"""References and the tolerance rule of the edge-case tests of the two side kernels that feed SAGA's feature training:
-the KNN feature smoothing (tests/test_knn_smooth_edges.py) and the contrastive front end
-(tests/test_contrastive_frontend_edges.py).
+"""References and the tolerance rule of the edge-case tests of the side kernels that feed SAGA's feature training:
+the KNN feature smoothing (tests/test_knn_smooth_edges.py), its multi-resolution form (tests/test_multi_res_smooth_edges.py) and
+the contrastive front end (tests/test_contrastive_frontend_edges.py).
 
 The rule is the one of tests/photometric_ref.py (FACTOR, FLOOR), applied per GROUP of equal scale, never per whole tensor:
 
@@ -87,6 +87,83 @@ def knn_check(name, F, idx, cols, g, normalize_out, out, dF):
     assert (r_o <= 1.0).all(), (name, "out", int(np.argmax(~(r_o <= 1.0))), float(np.nanmax(r_o)))
     assert (r_g <= 1.0).all(), (name, "dL/dF", int(np.argmax(~(r_g <= 1.0))), float(np.nanmax(r_g)))
     return float(r_o.max()), float(r_g.max())
+
+
+# ---- multi-resolution KNN feature smoothing ------------------------------------------------------------------------------------
+
+MULTI_OUT_FLOOR = FLOOR            # floor of an out row                     } confirmed by two float32 evaluation orders on every
+MULTI_GRAD_FLOOR = KNN_GRAD_FLOOR  # floor of a dL/dF_j row                  } case of tests/test_multi_res_smooth_edges.py (figures
+MULTI_DW_FLOOR = FLOOR             # floor of a dL/dw entry / row            } in that module's docstring)
+
+
+def multi_res_magnitudes(F, levels, w, g, normalize_out):
+    """Magnitude of the terms summed into every group of the multi-resolution smoothing (tests/multi_res_smooth_ref.py), float64:
+    out_i   : largest channel of sum_l |w_il| (1/k_l) sum_s |n_idx(i,l,s)|, divided by |ret_i| + 1e-9 when normalize_out;
+    dL/dF_j : largest channel of sum over the references (i, l, s) to j of (|w_il| / k_l) T_i, divided by max(|F_j|, 1e-12), with
+              T_i the terms of dL/dret_i per channel: |g_i|, or |g_i| a + |ret_i| |b| under normalize_out (a = 1 / (r + 1e-9),
+              b = (ret_i . g_i) a^2 / r, 0 at r = 0; r = |ret_i|);
+    dL/dw   : |T_i| |mean_{l,i}| (Cauchy-Schwarz) per entry (i, l); under normalize_out one value per row i, the largest over l
+              (the entries of a row cancel against each other there); summed over i for one shared row of weights.
+    Returns (mag_out (P,), mag_dF (P,), mag_dw or None): mag_dw has the shape of dL/dw without normalize_out, and one value per
+    row of dL/dw with it."""
+    F, g = np.asarray(F, np.float64), np.asarray(g, np.float64)
+    P, L = F.shape[0], len(levels)
+    nrm = np.maximum(np.linalg.norm(F, axis=1, keepdims=True), 1e-12)
+    n = F / nrm
+    gidx = [np.flatnonzero(np.asarray(pm, bool))[np.asarray(idx, np.int64)] for pm, idx in levels]      # global indices, (P, k_l)
+    W = np.ones((P, L)) if w is None else np.broadcast_to(np.asarray(w, np.float64), (P, L))
+    means = [n[gi, :].mean(axis=1) for gi in gidx]
+    ret = sum(W[:, l:l + 1] * means[l] for l in range(L))
+    mag_out = sum(np.abs(W[:, l:l + 1]) * np.abs(n)[gidx[l], :].mean(axis=1) for l in range(L)).max(axis=1)
+    T = np.abs(g)
+    if normalize_out:
+        r = np.linalg.norm(ret, axis=1, keepdims=True)
+        a = 1.0 / (r + 1e-9)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            b = np.where(r > 0, (ret * g).sum(axis=1, keepdims=True) * a * a / r, 0.0)
+        mag_out = mag_out / (r[:, 0] + 1e-9)
+        T = T * a + np.abs(ret) * np.abs(b)
+    acc = np.zeros_like(F)
+    for l, gi in enumerate(gidx):
+        contrib = np.abs(W[:, l:l + 1]) / gi.shape[1] * T
+        for s in range(gi.shape[1]):
+            np.add.at(acc, gi[:, s], contrib)
+    mag_dF = acc.max(axis=1) / nrm[:, 0]
+    if w is None:
+        return mag_out, mag_dF, None
+    terms = np.stack([np.linalg.norm(T, axis=1) * np.linalg.norm(m, axis=1) for m in means], axis=1)   # (P, L)
+    if np.asarray(w).shape[0] == 1:
+        terms = terms.sum(axis=0, keepdims=True)
+    return mag_out, mag_dF, terms.max(axis=1) if normalize_out else terms
+
+
+def multi_res_check(name, F, levels, w, g, normalize_out, out, dF, dw):
+    """The rule for one run of the multi-resolution smoothing: truth is multi_res_smooth_ref.forward_backward (float64 autograd),
+    E32 comes from multi_res_smooth_ref.expression in float32 on the CPU.  Groups: every out row, every dL/dF row, and of dL/dw
+    every entry (without normalize_out) or every row (with it).  Prints error / bound per class, asserts every group, returns the
+    worst per class (dL/dw: None without weights)."""
+    from tests import multi_res_smooth_ref as mref
+    want_o, want_g, want_w = mref.forward_backward(F, levels, w, normalize_out, g)
+    o32, g32, w32 = mref.float32_expression(F, levels, w, normalize_out, g)
+    mag_o, mag_g, mag_w = multi_res_magnitudes(F, levels, w, g, normalize_out)
+    r_o = ratios(out, want_o, o32, mag_o, rows=True, floor=MULTI_OUT_FLOOR)
+    r_g = ratios(dF, want_g, g32, mag_g, rows=True, floor=MULTI_GRAD_FLOOR)
+    classes = [("out rows", r_o), ("dL/dF rows", r_g)]
+    if w is None:
+        assert dw is None, (name, "dL/dw without weights")
+    else:
+        dw = np.asarray(dw, np.float64)
+        assert dw.shape == want_w.shape, (name, "dL/dw shape", dw.shape, want_w.shape)
+        if normalize_out:
+            r_w = ratios(dw, want_w, w32, mag_w, rows=True, floor=MULTI_DW_FLOOR)
+        else:
+            r_w = ratios(dw[..., None], want_w[..., None], w32[..., None], mag_w, rows=True, floor=MULTI_DW_FLOOR).reshape(-1)
+        classes.append(("dL/dw rows" if normalize_out else "dL/dw entries", r_w))
+    worst = [float("nan") if np.isnan(r).any() else float(r.max()) for _, r in classes]
+    print(f"{name}: error / bound  " + "  ".join(f"{k} {v:.3f}" for (k, _), v in zip(classes, worst)))
+    for (k, r), v in zip(classes, worst):
+        assert (r <= 1.0).all(), (name, k, int(np.argmax(~(r <= 1.0))), v)
+    return tuple(worst) + ((None,) if w is None else ())
 
 
 # ---- contrastive front end ----------------------------------------------------------------------------------------------------

@@ -17,19 +17,40 @@ def _f64(a, requires_grad=False):
     return t.requires_grad_(requires_grad)
 
 
-def expression(f, levels, w, normalize_out):
+def expression(f, levels, w, normalize_out, channel_perm=None, reverse=False):
     """The expression itself on torch tensors `f` (P, C) and `w` (None, (P, L) or (1, L)) of one dtype, written the way the
-    reference writes it (so that it also serves, in float32, as the measure of the reference's own rounding noise)."""
+    reference writes it (so that it also serves, in float32, as the measure of the reference's own rounding noise).
+    channel_perm / reverse give the same expression another float evaluation order, forward and (through autograd) backward:
+    the channels permuted before and restored after; the levels walked, and each level's columns gathered, last to first."""
+    if channel_perm is not None:
+        perm = torch.as_tensor(np.asarray(channel_perm), dtype=torch.int64)
+        f = f[:, perm]
     normed = torch.nn.functional.normalize(f, dim=-1, p=2)
     ret = torch.zeros_like(normed)
-    for l, (pm, idx) in enumerate(levels):
+    order = range(len(levels) - 1, -1, -1) if reverse else range(len(levels))
+    for l in order:
+        pm, idx = levels[l]
         pm = torch.as_tensor(np.asarray(pm), dtype=torch.bool)
         idx = torch.as_tensor(np.asarray(idx), dtype=torch.int64)
+        if reverse:
+            idx = idx.flip(1)
         sw = w[:, l:l + 1] if w is not None else 1
         ret = ret + sw * normed[pm][idx, :].mean(dim=1)
     if normalize_out:
         ret = ret / (ret.norm(dim=1, keepdim=True) + 1e-9)
+    if channel_perm is not None:
+        ret = ret[:, torch.argsort(perm)]
     return ret
+
+
+def float32_expression(F, levels, w, normalize_out, grad_out, channel_perm=None, reverse=False):
+    """(out, dL/dF, dL/dw or None) of `expression` in float32 torch on the CPU, as float64 numpy arrays: the yardstick E32 of
+    tests/edge_ref.py, and with channel_perm / reverse the alternative evaluation orders that confirm its floors."""
+    f = torch.as_tensor(np.asarray(F), dtype=torch.float32).clone().requires_grad_(True)
+    wt = None if w is None else torch.as_tensor(np.asarray(w), dtype=torch.float32).clone().requires_grad_(True)
+    out = expression(f, levels, wt, normalize_out, channel_perm, reverse)
+    out.backward(torch.as_tensor(np.asarray(grad_out), dtype=torch.float32))
+    return (out.detach().double().numpy(), f.grad.double().numpy(), None if wt is None else wt.grad.double().numpy())
 
 
 def make_levels(xyz, masks, Ks):
@@ -102,11 +123,7 @@ def dw_term_scale(F, levels, w, normalize_out, grad_out):
 def fp32_reference_error(F, levels, w, normalize_out, grad_out, want):
     """The reference expression evaluated in float32 torch on the CPU against `want` = forward_backward(...) of the same inputs:
     max |error| / max |want| of out, dL/dF and dL/dw (None without weights) -- the rounding noise of the reference itself."""
-    f = torch.as_tensor(np.asarray(F), dtype=torch.float32).clone().requires_grad_(True)
-    wt = None if w is None else torch.as_tensor(np.asarray(w), dtype=torch.float32).clone().requires_grad_(True)
-    out = expression(f, levels, wt, normalize_out)
-    out.backward(torch.as_tensor(np.asarray(grad_out), dtype=torch.float32))
-    got = (out.detach().numpy(), f.grad.numpy(), None if wt is None else wt.grad.numpy())
+    got = float32_expression(F, levels, w, normalize_out, grad_out)
     return tuple(None if b is None else float(np.abs(a - b).max() / np.abs(b).max()) for a, b in zip(got, want))
 
 
