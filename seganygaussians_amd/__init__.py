@@ -45,6 +45,18 @@ def install_dropin(fuse_smoothing: bool = False, fuse_training_step: bool = Fals
     return DROPIN_DIR
 
 
+# the viewer frame (viewer.py), resolved on first use so that importing the package stays free of torch
+_VIEWER_NAMES = ("ViewerFrame", "feature_covariance", "feature_pca_basis", "gui_pca_sample", "prompt_features", "viewer_frame")
+__all__ = ["install_dropin", "patch_feature_model", "patch_gaussian_model"] + list(_VIEWER_NAMES)
+
+
+def __getattr__(name):
+    if name in _VIEWER_NAMES:
+        from . import viewer
+        return getattr(viewer, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 _FF_MODULE = "scene.gaussian_model_ff"
 _GM_MODULE = "scene.gaussian_model"
 

@@ -27,6 +27,9 @@ LIFT_EXPORTS = ["mi_rast_lift", "mi_rast_lift_reuse"]
 MI_RAST_LIFT_MAX_CHANNELS = 64
 # include/mi_segment.h, its vote-graph section (csrc/mi_vote_graph.hip); listed on its own and as the tail of EXPORTS
 VOTE_GRAPH_EXPORTS = ["mi_vote_mask_features_workspace_bytes", "mi_vote_mask_features", "mi_vote_anchor_bits", "mi_vote_relevancy"]
+# include/mi_segment.h, its viewer-frame section (csrc/mi_viewer.hip); listed on its own and as the tail of EXPORTS
+VIEWER_EXPORTS = ["mi_view_moments_workspace_bytes", "mi_view_moments_block", "mi_view_moments", "mi_view_frame"]
+MI_VIEW_MODES = {"rgb": 1, "pca": 2, "cluster": 4, "similarity": 8}
 EXPORTS = [
     "mi_rast_forward", "mi_rast_forward_reuse", "mi_rast_last_longest_run", "mi_rast_fingerprint", "mi_rast_features_only_supported", "mi_rast_backward", "mi_rast_mark_visible", "mi_rast_mask_forward",
     "mi_rast_mask_backward", "mi_rast_last_error", "mi_rast_version", "mi_rast_supported_channels",
@@ -37,7 +40,7 @@ EXPORTS = [
     "mi_contrastive_forward", "mi_contrastive_backward",  # include/mi_contrastive.h
     "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
     "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
-] + CLUSTER_EXPORTS + LIFT_EXPORTS + VOTE_GRAPH_EXPORTS
+] + CLUSTER_EXPORTS + LIFT_EXPORTS + VOTE_GRAPH_EXPORTS + VIEWER_EXPORTS
 # include/mi_mask_scales.h, its mask-sets section (csrc/mi_mask_sets.hip); listed on its own and as the tail of MASK_SCALES_EXPORTS
 MASK_SETS_EXPORTS = ["mi_mask_overlaps", "mi_mask_boxes", "mi_mask_nms_keep", "mi_mask_score_images"]
 MI_MASK_SCORE_MODE = {"sum": 0, "mean": 1, "max": 2}
@@ -231,6 +234,14 @@ def load():
     L.mi_vote_anchor_bits.argtypes = [i, i, i, vp, vp, vp, f, vp, vp, vp]
     L.mi_vote_relevancy.restype = i
     L.mi_vote_relevancy.argtypes = [i, i, i, i, vp, i, vp, vp, i, vp, vp]
+    L.mi_view_moments_workspace_bytes.restype = C.c_size_t
+    L.mi_view_moments_workspace_bytes.argtypes = [i, i]
+    L.mi_view_moments_block.restype = i
+    L.mi_view_moments_block.argtypes = []
+    L.mi_view_moments.restype = i
+    L.mi_view_moments.argtypes = [i, i, i, vp, vp, i, i, vp, C.c_size_t, vp, vp, vp]
+    L.mi_view_frame.restype = i
+    L.mi_view_frame.argtypes = [i, i, vp, vp, vp, vp, i, vp, vp, f, i, i, vp, vp, vp, vp]
     _lib = L
     return L
 

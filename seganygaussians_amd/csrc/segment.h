@@ -20,6 +20,7 @@
 #pragma once
 
 #include "../../include/mi_segment.h"
+#include "seg_row.h"   // seg_row_scale, seg_accumulate, seg_select: shared with viewer.h
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -54,26 +55,6 @@ __host__ __device__ constexpr int seg_assign_block(int NS)
     return SEG_GEMM_LDS_FLOATS / (2 * NS + 1) / 32 * 32 > 512 ? 512 : SEG_GEMM_LDS_FLOATS / (2 * NS + 1) / 32 * 32;
 }
 
-// s_k = d_k * scale: a = u / f of the header's `pre`, then F.normalize of v = a (f g) when post is set
-__device__ inline float seg_row_scale(float n1, float n2, int pre, int post)
-{
-    float a = 1.f;
-    if (pre == MI_SEGMENT_PRE_L2) a = 1.f / fmaxf(sqrtf(n1), 1e-12f);
-    else if (pre == MI_SEGMENT_PRE_EPS) a = 1.f / (sqrtf(n1) + 1e-6f);
-    if (post) a = a / fmaxf(a * sqrtf(n2), 1e-12f);
-    return a;
-}
-
-template <int QT>
-__device__ inline void seg_accumulate(float f, float g, const float* __restrict__ qc, float& n1, float& n2, float (&d)[QT])
-{
-    const float t = f * g;
-    n1 = fmaf(f, f, n1);
-    n2 = fmaf(t, t, n2);
-#pragma unroll
-    for (int k = 0; k < QT; k++) d[k] = fmaf(t, qc[k], d[k]);
-}
-
 template <int QT>
 __device__ inline void seg_finish(const SegArgs& a, long long n, float n1, float n2, const float (&d)[QT])
 {
@@ -83,17 +64,9 @@ __device__ inline void seg_finish(const SegArgs& a, long long n, float n1, float
         for (int k = 0; k < QT; k++)
             if (k < a.Q) a.out_f[(size_t)k * a.N + n] = d[k] * scale;
     } else if (a.mode == SEG_SELECT) {
-        bool any = false;
-        float top = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < QT; k++)
-            if (k < a.Q) {
-                float t = d[k] * scale;
-                if (a.half_shift) t = (t + 1.f) * 0.5f;
-                const bool b = t > a.threshold;
-                any = any || b;
-                top = fmaxf(top, b ? t : 0.f);
-            }
+        bool any;
+        float top;
+        seg_select<QT>(d, scale, a.Q, a.half_shift, a.threshold, any, top);
         a.mask[n] = any ? 1 : 0;
         a.out_f[n] = top;
     } else {

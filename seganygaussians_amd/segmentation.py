@@ -85,7 +85,8 @@ def similarity_scores(features: torch.Tensor, queries: torch.Tensor, gates: torc
     """s_k of every row for 1 <= Q <= 16 queries: (Q, H, W) for a (C, H, W) image, (Q, P) for (P, C) points.
 
     saga_gui.py:592-599 + :645 is similarity_scores(rendered, chosen.T, gates, pre="eps"); :593, the PCA image, is
-    similarity_scores(rendered, proj_mat.T, pre="eps", post=False) (clip(x * 0.5 + 0.5, 0, 1) stays with the caller).
+    similarity_scores(rendered, proj_mat.T, pre="eps", post=False); viewer.viewer_frame() applies clip(x * 0.5 + 0.5, 0, 1) of :594
+    to the same chain and composes the display buffer in the one read of the image.
     features: float32 (C, H, W) or (P, C); a non-contiguous tensor is copied.  queries: float32 (Q, C) or (C,), used as given.
     gates: float32, C values, or None."""
     from . import _lib
