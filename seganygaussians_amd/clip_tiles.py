@@ -20,9 +20,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import check_out, number, size_hw
 from ._ffi import check, stream_ptr
-from .mask_scales import _as_packed, _size
-from .sam_masks import _check_shape, resize_sam_masks
+from .mask_scales import as_packed, check_shape
+from .sam_masks import resize_sam_masks
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # clip_utils/clip_utils.py:64
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)   # clip_utils/clip_utils.py:65
@@ -70,7 +71,7 @@ def clip_tiles(image, masks, size=(224, 224), layout: str = "crop", background=N
 
     out: an optional contiguous (M, 3, Sh, Sw) tensor of `dtype` on the masks' GPU to write into.  Deterministic: no atomics."""
     who = "clip_tiles"
-    Sh, Sw = _size(size, who)
+    Sh, Sw = size_hw(who, size)
     if Sh > MAX_SIZE or Sw > MAX_SIZE:
         raise ValueError(f"{who}: need 1 <= Sh, Sw <= {MAX_SIZE}, got {(Sh, Sw)}")
     if layout not in _lib.MI_CLIP_TILES_LAYOUT:
@@ -79,12 +80,7 @@ def clip_tiles(image, masks, size=(224, 224), layout: str = "crop", background=N
         raise ValueError(f"{who}: dtype must be torch.float16 or torch.float32, got {dtype}")
     if background is None:
         background = _DEFAULT_BACKGROUND[layout]
-    try:
-        background = float(background)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: background must be a number, got {background!r}") from None
-    if background != background:
-        raise ValueError(f"{who}: background is NaN")
+    background = number(who, "background", background)
     bg = float(np.float32(np.float32(255.0 * background) / np.float32(255.0)))
     mean_c, std_c = _triple(mean, "mean"), _triple(std, "std")
     if any(s == 0.0 for s in std_c):
@@ -98,11 +94,8 @@ def clip_tiles(image, masks, size=(224, 224), layout: str = "crop", background=N
     if tuple(int(v) for v in getattr(masks, "shape", ()))[1:] != (H, W):
         raise ValueError(f"{who}: the masks {tuple(getattr(masks, 'shape', ()))} are not at the image's size {(H, W)}; "
                          f"resize_sam_masks(masks, {(H, W)}) brings them there")
-    _check_shape(masks, who)
-    try:
-        packed = _as_packed(masks, image.device if image.is_cuda else None, who)   # CPU masks go to the image's GPU
-    except ValueError as e:
-        raise ValueError(str(e).replace("the depth on", "the image on")) from None
+    check_shape(who, masks)
+    packed = as_packed(who, masks, image.device if image.is_cuda else None, "image")   # CPU masks go to the image's GPU
     M = packed.shape[0]
     dev = packed.device
     if image.device != dev:
@@ -118,9 +111,8 @@ def clip_tiles(image, masks, size=(224, 224), layout: str = "crop", background=N
             raise ValueError(f"{who}: inclusive applies to the masks' own boxes; rects are half-open as given")
     if out is None:
         out = torch.empty((M, 3, Sh, Sw), device=dev, dtype=dtype)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (M, 3, Sh, Sw) or out.dtype != dtype or out.device != dev \
-            or not out.is_contiguous():
-        raise ValueError(f"{who}: out must be a contiguous {dtype} ({M}, 3, {Sh}, {Sw}) tensor on {dev}")
+    else:
+        check_out(who, out, (M, 3, Sh, Sw), dtype, dev, dtype_name=str(dtype))
     L = _lib.load()
     boxes = torch.empty((M, 4), device=dev, dtype=torch.float32)
     areas = torch.empty((M,), device=dev, dtype=torch.int64)

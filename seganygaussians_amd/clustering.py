@@ -19,6 +19,7 @@ import ctypes
 
 import torch
 
+from ._args import no_grad_one_gpu, to_float
 from ._ffi import check, stream_ptr
 
 METRICS = {"euclidean": 0, "jaccard": 1}
@@ -47,10 +48,7 @@ def pack_bits(bool_matrix: torch.Tensor) -> torch.Tensor:
 def _check_params(who, min_cluster_size, cluster_selection_epsilon, n=1):
     if not isinstance(min_cluster_size, int) or isinstance(min_cluster_size, bool) or min_cluster_size < 2:
         raise ValueError(f"{who}: min_cluster_size must be an integer >= 2, got {min_cluster_size!r}")
-    try:
-        eps = float(cluster_selection_epsilon)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: cluster_selection_epsilon must be a number, got {cluster_selection_epsilon!r}") from None
+    eps = to_float(who, "cluster_selection_epsilon", cluster_selection_epsilon)
     if not eps >= 0.0 or eps == float("inf"):
         raise ValueError(f"{who}: cluster_selection_epsilon must be finite and >= 0, got {cluster_selection_epsilon!r}")
     if not 1 <= n <= MAX_POINTS:
@@ -79,10 +77,7 @@ def _prepare(who: str, points, core_k, metric):
         raise ValueError(f"{who}: core_k must be an integer in 1..{MAX_CORE_K}, got {core_k!r}")
     if core_k > n:
         raise ValueError(f"{who}: need n >= core_k, got n = {n}, core_k = {core_k}")
-    if torch.is_grad_enabled() and points.requires_grad:
-        raise ValueError(f"{who}: points requires grad and there is no backward; call under torch.no_grad() or detach it")
-    if not points.is_cuda:
-        raise ValueError(f"{who}: points must be on a GPU, got {points.device} (there is no CPU fallback)")
+    no_grad_one_gpu(who, [("points", points)])
     return points.detach().contiguous(), METRICS[metric], n, width
 
 

@@ -17,11 +17,29 @@ import math
 
 import torch
 
+from ._args import f32, number, size_hw
 from ._ffi import check, stream_ptr
 from .contrastive_loss import MAX_MASKS, PackedSamMasks, pack_sam_masks
 
+MAX_PIXELS = 1 << 24
 
-def _as_packed(masks, dev, who: str) -> PackedSamMasks:
+
+def check_shape(who: str, masks) -> None:
+    """The limits of sam_masks.py and clip_tiles.py that need no device, before anything is packed or launched (the rest is
+    as_packed's)."""
+    if not isinstance(masks, PackedSamMasks) and not (isinstance(masks, torch.Tensor) and masks.dtype == torch.bool and masks.dim() == 3):
+        raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got "
+                         f"{getattr(masks, 'dtype', type(masks))} {tuple(getattr(masks, 'shape', ()))}")
+    M, h, w = (int(v) for v in masks.shape)
+    if not 1 <= M <= MAX_MASKS:
+        raise ValueError(f"{who}: need 1 <= M <= {MAX_MASKS} masks, got {M}")
+    if h * w >= MAX_PIXELS:
+        raise ValueError(f"{who}: need h * w < 2^24 pixels, got {h} x {w}")
+
+
+def as_packed(who: str, masks, dev, versus: str = "depth") -> PackedSamMasks:
+    """masks as a PackedSamMasks on the GPU dev (None: on their own GPU, or the current one for CPU masks).  versus names the
+    tensor whose GPU dev is, for the message about masks that are elsewhere."""
     if isinstance(masks, PackedSamMasks):
         M, h, w = masks.shape
         words = masks.words
@@ -31,30 +49,20 @@ def _as_packed(masks, dev, who: str) -> PackedSamMasks:
             raise ValueError(f"{who}: PackedSamMasks words must be int64 ({M}, {h}, {(w + 63) // 64}) on a GPU, got "
                              f"{words.dtype} {tuple(words.shape)} on {words.device}")
         if dev is not None and words.device != dev:
-            raise ValueError(f"{who}: the masks are on {words.device}, the depth on {dev}")
+            raise ValueError(f"{who}: the masks are on {words.device}, the {versus} on {dev}")
         return PackedSamMasks(words.contiguous(), (M, h, w))
     if isinstance(masks, torch.Tensor):
         if masks.dtype != torch.bool or masks.dim() != 3:
             raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got {masks.dtype} {tuple(masks.shape)}")
         if masks.is_cuda and dev is not None and masks.device != dev:
-            raise ValueError(f"{who}: the masks are on {masks.device}, the depth on {dev}")
+            raise ValueError(f"{who}: the masks are on {masks.device}, the {versus} on {dev}")
         if not masks.is_cuda and masks.device.type != "cpu":
             raise ValueError(f"{who}: masks on {masks.device}; need the CPU or a GPU")
         return pack_sam_masks(masks, device=dev)   # checks M and the image size
     raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got {type(masks)}")
 
 
-def _size(size, who: str):
-    try:
-        H, W = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: size must be (H, W), got {size!r}") from None
-    if H < 1 or W < 1:
-        raise ValueError(f"{who}: size must be positive, got {(H, W)}")
-    return H, W
-
-
-def _erode(packed: PackedSamMasks, H: int, W: int, min_sum: float = 5.0) -> PackedSamMasks:
+def erode(packed: PackedSamMasks, H: int, W: int, min_sum: float = 5.0) -> PackedSamMasks:
     from . import _lib
     L = _lib.load()
     M, h, w = packed.shape
@@ -67,16 +75,6 @@ def _erode(packed: PackedSamMasks, H: int, W: int, min_sum: float = 5.0) -> Pack
     return PackedSamMasks(out, (M, H, W))
 
 
-def _min_sum(min_sum, who: str) -> float:
-    try:
-        v = float(min_sum)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: min_sum must be a number, got {min_sum!r}") from None
-    if v != v:
-        raise ValueError(f"{who}: min_sum is NaN")
-    return v
-
-
 def erode_sam_masks(masks, size, min_sum=5) -> PackedSamMasks:
     """get_scale.py:145-152: F.interpolate(masks[:, None], size, mode='bilinear', align_corners=False), conv2d with a 3x3 box of
     ones (zero padding) and >= min_sum (5 there; the notebook's language section has 2), bit-packed.
@@ -84,10 +82,10 @@ def erode_sam_masks(masks, size, min_sum=5) -> PackedSamMasks:
     masks: bool (M, h, w) on the CPU or a GPU (packed here), or a PackedSamMasks (padding bits 0, as pack_sam_masks writes them);
     size: the output (H, W).  Returns the eroded masks as a PackedSamMasks (M, H, ceil(W / 64)) on the masks' GPU (the current GPU
     for CPU masks), padding bits 0."""
-    H, W = _size(size, "erode_sam_masks")
-    min_sum = _min_sum(min_sum, "erode_sam_masks")
-    packed = _as_packed(masks, None, "erode_sam_masks")
-    return _erode(packed, H, W, min_sum)
+    H, W = size_hw("erode_sam_masks", size)
+    min_sum = number("erode_sam_masks", "min_sum", min_sum)
+    packed = as_packed("erode_sam_masks", masks, None)
+    return erode(packed, H, W, min_sum)
 
 
 def sam_mask_scales(depth: torch.Tensor, masks, fovx: float, fovy: float, return_counts: bool = False):
@@ -101,8 +99,7 @@ def sam_mask_scales(depth: torch.Tensor, masks, fovx: float, fovy: float, return
     pairs them; NaN for a mask with fewer than 2 eroded pixels.  With return_counts, also the eroded pixel counts (M,) int64.
     M = 1 follows the same formula (the reference's .squeeze() at :152 drops the mask axis there and breaks)."""
     from . import _lib
-    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32:
-        raise ValueError(f"sam_mask_scales: depth must be a float32 tensor, got {getattr(depth, 'dtype', type(depth))}")
+    f32("sam_mask_scales", "depth", depth)
     if depth.dim() == 3 and depth.shape[0] == 1:
         depth = depth[0]
     if depth.dim() != 2:
@@ -116,14 +113,14 @@ def sam_mask_scales(depth: torch.Tensor, masks, fovx: float, fovy: float, return
     if not (0.0 < fovx < math.pi and 0.0 < fovy < math.pi):
         raise ValueError(f"sam_mask_scales: need 0 < fovx, fovy < pi radians, got {(fovx, fovy)}")
     dev = depth.device
-    packed = _as_packed(masks, dev, "sam_mask_scales")
+    packed = as_packed("sam_mask_scales", masks, dev)
     M = packed.shape[0]
     if M * H * ((W + 63) // 64) >= 1 << 31:
         raise ValueError("sam_mask_scales: more than 2^31 mask words")
     # :138-139 in float64 (numpy's tan of the Python floats FoVx / FoVy)
     fx = (W / 2) / math.tan(fovx / 2)
     fy = (H / 2) / math.tan(fovy / 2)
-    eroded = _erode(packed, H, W)
+    eroded = erode(packed, H, W)
     L = _lib.load()
     depth = depth.contiguous()
     ws = torch.empty((L.mi_mask_scales_workspace_bytes(M, H, W),), device=dev, dtype=torch.uint8)

@@ -18,6 +18,7 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
+from ._args import f32, number
 from ._ffi import check, stream_ptr
 
 WINDOW_SIZE = 11
@@ -28,8 +29,7 @@ _L1, _SSIM = 1, 2             # MI_PHOTO_L1, MI_PHOTO_SSIM
 def _prepare(who: str, image, gt, names=("image", "gt")):
     """Checks everything that can be checked without a device; returns (B, C, H, W).  Raises ValueError before any launch."""
     for name, t in zip(names, (image, gt)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise ValueError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+        f32(who, name, t)
     if image.dim() not in (3, 4):
         raise ValueError(f"{who}: {names[0]} must be (C, H, W) or (B, C, H, W), got {tuple(image.shape)}")
     if image.shape != gt.shape:
@@ -124,12 +124,7 @@ def photometric_loss(image: torch.Tensor, gt: torch.Tensor, lambda_dssim: float 
     image, gt: float32 (C, H, W) or (B, C, H, W) on one GPU; a non-contiguous tensor is copied once.  Returns the loss as a 0-dim
     float32 tensor, differentiable with respect to image; with return_parts also the detached Ll1 and ssim scalars
     (training_report logs Ll1).  The gradient is written in image's own layout by autograd."""
-    try:
-        lambda_dssim = float(lambda_dssim)
-    except (TypeError, ValueError):
-        raise ValueError(f"photometric_loss: lambda_dssim must be a number, got {lambda_dssim!r}") from None
-    if lambda_dssim != lambda_dssim:
-        raise ValueError("photometric_loss: lambda_dssim is NaN")
+    lambda_dssim = number("photometric_loss", "lambda_dssim", lambda_dssim)
     dims = _prepare("photometric_loss", image, gt)
     loss, l1, ss = _PhotometricLoss.apply(image, gt.detach(), dims, lambda_dssim, 0)
     return (loss, l1, ss) if return_parts else loss

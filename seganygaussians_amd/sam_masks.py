@@ -21,45 +21,23 @@ from __future__ import annotations
 import torch
 
 from . import _lib
+from ._args import check_out, f32, number, size_hw
 from ._ffi import check, stream_ptr
 from .contrastive_loss import MAX_MASKS, PackedSamMasks
-from .mask_scales import _as_packed, _size
+from .mask_scales import MAX_PIXELS, as_packed, check_shape
 
-MAX_PIXELS = 1 << 24
 MAX_SCORE_COLUMNS = _lib.MI_MASK_SCORE_MAX_COLUMNS
-
-
-def _f32(t, name: str, who: str) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
-    return t
-
-
-def _check_shape(masks, who: str):
-    """The limits that need no device, before anything is packed or launched (the rest is _as_packed's)."""
-    if not isinstance(masks, PackedSamMasks) and not (isinstance(masks, torch.Tensor) and masks.dtype == torch.bool and masks.dim() == 3):
-        raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got "
-                         f"{getattr(masks, 'dtype', type(masks))} {tuple(getattr(masks, 'shape', ()))}")
-    M, h, w = (int(v) for v in masks.shape)
-    if not 1 <= M <= MAX_MASKS:
-        raise ValueError(f"{who}: need 1 <= M <= {MAX_MASKS} masks, got {M}")
-    if h * w >= MAX_PIXELS:
-        raise ValueError(f"{who}: need h * w < 2^24 pixels, got {h} x {w}")
 
 
 def _packed(masks, scores, who: str) -> PackedSamMasks:
     """masks as a PackedSamMasks on the GPU of `scores` (None: on their own GPU, or the current one for CPU masks)."""
-    _check_shape(masks, who)
+    check_shape(who, masks)
     dev = None
     if scores is not None:
         if not scores.is_cuda:
             raise ValueError(f"{who}: scores must be on a GPU, got {scores.device}")
         dev = scores.device
-    try:
-        return _as_packed(masks, dev, who)
-    except ValueError as e:
-        # _as_packed words its device mismatch for sam_mask_scales' depth
-        raise ValueError(str(e).replace("the depth on", "the scores on")) from None
+    return as_packed(who, masks, dev, "scores")
 
 
 def _overlaps(packed: PackedSamMasks, order):
@@ -109,16 +87,6 @@ def masks_to_boxes(masks, return_areas: bool = False):
     return (boxes, areas) if return_areas else boxes
 
 
-def _threshold(v, name: str) -> float:
-    try:
-        v = float(v)
-    except (TypeError, ValueError):
-        raise ValueError(f"mask_nms: {name} must be a number, got {v!r}") from None
-    if v != v:
-        raise ValueError(f"mask_nms: {name} is NaN")
-    return v
-
-
 def mask_nms(masks, scores, iou_thr=0.7, score_thr=0.1, inner_thr=0.2, **kwargs):
     """clip_utils/sam_utils.py:123-187: mask non-maximum suppression.  Returns selected_idx (int64, on the scores' GPU), the kept
     masks in descending-score order, like the reference's idx[keep].
@@ -135,9 +103,9 @@ def mask_nms(masks, scores, iou_thr=0.7, score_thr=0.1, inner_thr=0.2, **kwargs)
         IndexError on the 1-D tensor it has (RuntimeError for M < 3).  Here the intent is built: that test is set true for the
         first min(3, M) masks of the sorted order.
       * ties in `scores` are ordered by a stable sort; the reference's order is unspecified there."""
-    scores = _f32(scores, "scores", "mask_nms")
-    iou_thr, score_thr = _threshold(iou_thr, "iou_thr"), _threshold(score_thr, "score_thr")
-    inner_max = 1.0 - _threshold(inner_thr, "inner_thr")   # :169-170 subtract in Python doubles; the comparison is in float32
+    f32("mask_nms", "scores", scores)
+    iou_thr, score_thr = number("mask_nms", "iou_thr", iou_thr), number("mask_nms", "score_thr", score_thr)
+    inner_max = 1.0 - number("mask_nms", "inner_thr", inner_thr)   # :169-170 subtract in Python doubles; the comparison is in float32
     packed = _packed(masks, scores, "mask_nms")
     M, dev = packed.shape[0], scores.device
     if tuple(scores.shape) != (M,):
@@ -183,7 +151,7 @@ def mask_score_images(scores, masks, mode: str = "mean", out=None):
                is count, and 0 / 1e-9 is 0)
       "max"  : max over all M masks of scores[m, k] * bit_m(p): a mask that does not cover p contributes 0   (get_scores, :206)
     out: an optional contiguous float32 (K, h, w) tensor on that GPU to write into.  Deterministic: no atomics."""
-    scores = _f32(scores, "scores", "mask_score_images")
+    f32("mask_score_images", "scores", scores)
     if mode not in _lib.MI_MASK_SCORE_MODE:
         raise ValueError(f"mask_score_images: mode must be one of {sorted(_lib.MI_MASK_SCORE_MODE)}, got {mode!r}")
     if scores.dim() not in (1, 2):
@@ -198,9 +166,8 @@ def mask_score_images(scores, masks, mode: str = "mean", out=None):
         raise ValueError(f"mask_score_images: {int(scores.shape[0])} score rows for {M} masks")
     if out is None:
         out = torch.empty((K, h, w), device=dev, dtype=torch.float32)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (K, h, w) or out.dtype != torch.float32 or out.device != dev \
-            or not out.is_contiguous():
-        raise ValueError(f"mask_score_images: out must be a contiguous float32 ({K}, {h}, {w}) tensor on {dev}")
+    else:
+        check_out("mask_score_images", out, (K, h, w), torch.float32, dev)
     s = scores.detach().contiguous()
     with torch.cuda.device(dev):
         check(_lib.load().mi_mask_score_images(M, h, w, K, packed.words.data_ptr(), s.data_ptr(), _lib.MI_MASK_SCORE_MODE[mode],
@@ -216,15 +183,10 @@ def resize_sam_masks(masks, size, threshold=0.5) -> PackedSamMasks:
     masks: bool (M, h, w) on the CPU or a GPU (packed here), or a PackedSamMasks; size: (H, W) with H * W < 2^24.  Returns a
     PackedSamMasks (M, H, ceil(W / 64)) on the masks' GPU (the current one for CPU masks), padding bits 0.  At the same size the
     value is the bit itself, so the result is a copy for 0 <= threshold < 1.  One launch."""
-    H, W = _size(size, "resize_sam_masks")
+    H, W = size_hw("resize_sam_masks", size)
     if H * W >= MAX_PIXELS:
         raise ValueError(f"resize_sam_masks: need H * W < 2^24 pixels, got {H} x {W}")
-    try:
-        threshold = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f"resize_sam_masks: threshold must be a number, got {threshold!r}") from None
-    if threshold != threshold:
-        raise ValueError("resize_sam_masks: threshold is NaN")
+    threshold = number("resize_sam_masks", "threshold", threshold)
     packed = _packed(masks, None, "resize_sam_masks")
     M, h, w = packed.shape
     dev = packed.device
@@ -248,9 +210,8 @@ def mask_index_map(masks, offset: int = 0, out=None) -> torch.Tensor:
     dev = packed.device
     if out is None:
         out = torch.empty((h, w), device=dev, dtype=torch.int32)
-    elif not isinstance(out, torch.Tensor) or tuple(out.shape) != (h, w) or out.dtype != torch.int32 or out.device != dev \
-            or not out.is_contiguous():
-        raise ValueError(f"mask_index_map: out must be a contiguous int32 ({h}, {w}) tensor on {dev}")
+    else:
+        check_out("mask_index_map", out, (h, w), torch.int32, dev)
     with torch.cuda.device(dev):
         check(_lib.load().mi_mask_index_map(M, h, w, packed.words.data_ptr(), offset, out.data_ptr(), stream_ptr(dev)))
     return out

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import torch
 
+from ._args import f32, no_grad_one_gpu, number
 from ._ffi import check, ptr, stream_ptr
 
 MAX_CHANNELS = 256
@@ -30,11 +31,9 @@ MAX_CENTERS = 4096
 PRE_MODES = {"none": 0, "l2": 1, "eps": 2}
 
 
-def _prepare(who: str, features, queries, gates, pre, max_q: int, qname: str):
-    """Checks everything that can be checked without a device, then returns (features, queries, gates, layout, N, C, Q, shape) with
-    contiguous tensors.  Raises ValueError before any pointer reaches the library."""
-    if not isinstance(features, torch.Tensor) or features.dtype != torch.float32:
-        raise ValueError(f"{who}: features must be a float32 tensor, got {getattr(features, 'dtype', type(features))}")
+def feature_table(who: str, features):
+    """(layout, C, N, shape) of a float32 feature image (C, H, W), layout 0, or feature table (P, C), layout 1, within the limits."""
+    f32(who, "features", features)
     if features.dim() == 3:
         layout, C, shape = 0, int(features.shape[0]), tuple(int(v) for v in features.shape[1:])
         N = shape[0] * shape[1]
@@ -47,8 +46,12 @@ def _prepare(who: str, features, queries, gates, pre, max_q: int, qname: str):
         raise ValueError(f"{who}: need 1 <= C <= {MAX_CHANNELS} channels, got {C}")
     if not 1 <= N < 1 << 31:
         raise ValueError(f"{who}: need 1 <= N < 2^31 rows, got {N}")
-    if not isinstance(queries, torch.Tensor) or queries.dtype != torch.float32:
-        raise ValueError(f"{who}: {qname} must be a float32 tensor, got {getattr(queries, 'dtype', type(queries))}")
+    return layout, C, N, shape
+
+
+def query_rows(who: str, queries, C: int, max_q: int, qname: str = "queries"):
+    """(queries as (Q, C), Q) of float32 (Q, C) or (C,) with 1 <= Q <= max_q."""
+    f32(who, qname, queries)
     if queries.dim() == 1:
         queries = queries[None]
     if queries.dim() != 2 or queries.shape[1] != C:
@@ -56,24 +59,31 @@ def _prepare(who: str, features, queries, gates, pre, max_q: int, qname: str):
     Q = int(queries.shape[0])
     if not 1 <= Q <= max_q:
         raise ValueError(f"{who}: need 1 <= {qname} <= {max_q}, got {Q}")
-    if gates is not None:
-        if not isinstance(gates, torch.Tensor) or gates.dtype != torch.float32:
-            raise ValueError(f"{who}: gates must be a float32 tensor or None, got {getattr(gates, 'dtype', type(gates))}")
-        if gates.numel() != C or gates.dim() > 2:
-            raise ValueError(f"{who}: gates must hold {C} values, got {tuple(gates.shape)}")
-        gates = gates.reshape(C)
+    return queries, Q
+
+
+def gate_row(who: str, gates, C: int):
+    """gates as (C,): float32 with C values in at most two dimensions, or None."""
+    if f32(who, "gates", gates, optional=True) is None:
+        return None
+    if gates.numel() != C or gates.dim() > 2:
+        raise ValueError(f"{who}: gates must hold {C} values, got {tuple(gates.shape)}")
+    return gates.reshape(C)
+
+
+def check_pre(who: str, pre) -> None:
     if pre not in PRE_MODES:
         raise ValueError(f"{who}: pre must be one of {sorted(PRE_MODES)}, got {pre!r}")
-    tensors = [("features", features), (qname, queries)] + ([("gates", gates)] if gates is not None else [])
-    if torch.is_grad_enabled():
-        for name, t in tensors:
-            if t.requires_grad:
-                raise ValueError(f"{who}: {name} requires grad and there is no backward; call under torch.no_grad() or detach it")
-    for name, t in tensors:
-        if not t.is_cuda:
-            raise ValueError(f"{who}: {name} must be on a GPU, got {t.device} (there is no CPU fallback)")
-        if t.device != features.device:
-            raise ValueError(f"{who}: {name} is on {t.device}, the features on {features.device}")
+
+
+def _prepare(who: str, features, queries, gates, pre, max_q: int, qname: str):
+    """Checks everything that can be checked without a device, then returns (features, queries, gates, layout, N, C, Q, shape) with
+    contiguous tensors.  Raises ValueError before any pointer reaches the library."""
+    layout, C, N, shape = feature_table(who, features)
+    queries, Q = query_rows(who, queries, C, max_q, qname)
+    gates = gate_row(who, gates, C)
+    check_pre(who, pre)
+    no_grad_one_gpu(who, [("features", features), (qname, queries)] + ([("gates", gates)] if gates is not None else []), "features")
     # a non-contiguous input (e.g. a transposed view) is copied once here
     features, queries = features.detach().contiguous(), queries.detach().contiguous()
     gates = None if gates is None else gates.detach().contiguous()
@@ -108,12 +118,7 @@ def select_by_similarity(features: torch.Tensor, queries: torch.Tensor, threshol
     (mask, score): mask bool = any_k t_k > threshold, score float32 = max_k (t_k > threshold ? t_k : 0), shaped (H, W) or (P,)."""
     from . import _lib
     features, queries, gates, layout, N, C, Q, shape = _prepare("select_by_similarity", features, queries, gates, pre, MAX_QUERIES, "queries")
-    try:
-        threshold = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f"select_by_similarity: threshold must be a number, got {threshold!r}") from None
-    if threshold != threshold:
-        raise ValueError("select_by_similarity: threshold is NaN")
+    threshold = number("select_by_similarity", "threshold", threshold)
     L = _lib.load()
     dev = features.device
     mask = torch.empty(shape, device=dev, dtype=torch.bool)

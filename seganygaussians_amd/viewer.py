@@ -22,32 +22,12 @@ from collections import namedtuple
 
 import torch
 
+from ._args import f32, no_grad_one_gpu, number
 from ._ffi import check, ptr, stream_ptr
 from ._lib import MI_VIEW_MODES as VIEW_MODES   # mode name -> MI_VIEW_* bit, in the order the components are added
-from .segmentation import MAX_CHANNELS, MAX_QUERIES, PRE_MODES
+from .segmentation import MAX_QUERIES, PRE_MODES, check_pre, feature_table, gate_row, query_rows
 
 ViewerFrame = namedtuple("ViewerFrame", ["frame", "mask", "score"])
-
-
-def _f32(who, name, t, optional=False):
-    if t is None and optional:
-        return
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"{who}: {name} must be a float32 tensor{' or None' if optional else ''}, got {getattr(t, 'dtype', type(t))}")
-
-
-def _no_grad_same_gpu(who, tensors):
-    """The checks that come last: no tensor asks for a gradient, all sit on the GPU of the first."""
-    if torch.is_grad_enabled():
-        for name, t in tensors:
-            if t.requires_grad:
-                raise ValueError(f"{who}: {name} requires grad and there is no backward; call under torch.no_grad() or detach it")
-    first = tensors[0][1]
-    for name, t in tensors:
-        if not t.is_cuda:
-            raise ValueError(f"{who}: {name} must be on a GPU, got {t.device} (there is no CPU fallback)")
-        if t.device != first.device:
-            raise ValueError(f"{who}: {name} is on {t.device}, the features on {first.device}")
 
 
 def _index_range(who, index, N):
@@ -75,19 +55,8 @@ def feature_covariance(features: torch.Tensor, index: torch.Tensor = None, pre: 
     Two launches, no atomics, bit-identical from run to run; the workspace is a torch allocation of this call."""
     from . import _lib
     who = "feature_covariance"
-    _f32(who, "features", features)
-    if features.dim() == 3:
-        layout, C, N = 0, int(features.shape[0]), int(features.shape[1]) * int(features.shape[2])
-    elif features.dim() == 2:
-        layout, C, N = 1, int(features.shape[1]), int(features.shape[0])
-    else:
-        raise ValueError(f"{who}: features must be (C, H, W) or (P, C), got {tuple(features.shape)}")
-    if not 1 <= C <= MAX_CHANNELS:
-        raise ValueError(f"{who}: need 1 <= C <= {MAX_CHANNELS} channels, got {C}")
-    if not 1 <= N < 1 << 31:
-        raise ValueError(f"{who}: need 1 <= N < 2^31 rows, got {N}")
-    if pre not in PRE_MODES:
-        raise ValueError(f"{who}: pre must be one of {sorted(PRE_MODES)}, got {pre!r}")
+    layout, C, N, _ = feature_table(who, features)
+    check_pre(who, pre)
     n = N
     if index is not None:
         if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1:
@@ -97,8 +66,7 @@ def feature_covariance(features: torch.Tensor, index: torch.Tensor = None, pre: 
             raise ValueError(f"{who}: need 1 <= len(index) < 2^31, got {n}")
         if not index.is_cuda:
             _index_range(who, index, N)
-    _no_grad_same_gpu(who, [("features", features)])
-    dev = features.device
+    dev = no_grad_one_gpu(who, [("features", features)])
     if index is not None:
         if index.is_cuda:
             if index.device != dev:
@@ -133,7 +101,7 @@ def feature_pca_basis(features: torch.Tensor, n_components: int = 3, index: torc
     features' device, eigenvalues (n_components,) float64 on the host), by descending eigenvalue.  do_pca is
     feature_pca_basis(point_features, 3, gui_pca_sample(P))."""
     who = "feature_pca_basis"
-    _f32(who, "features", features)
+    f32(who, "features", features)
     if features.dim() in (2, 3):
         C = int(features.shape[0] if features.dim() == 3 else features.shape[1])
         if not 1 <= int(n_components) <= C:
@@ -147,11 +115,11 @@ def prompt_features(features: torch.Tensor, yx, gates: torch.Tensor = None) -> t
     """The gated, normalised feature rows at clicked pixels (saga_gui.py:637, with :592 and :598-599): (Q, C), whose transpose is the
     reference's chosen_feature.  features (C, H, W); yx: Q pairs (y, x), wrapped modulo H and W as the reference wraps them."""
     who = "prompt_features"
-    _f32(who, "features", features)
+    f32(who, "features", features)
     if features.dim() != 3:
         raise ValueError(f"{who}: features must be (C, H, W), got {tuple(features.shape)}")
     C, H, W = (int(v) for v in features.shape)
-    _f32(who, "gates", gates, optional=True)
+    f32(who, "gates", gates, optional=True)
     if gates is not None and gates.numel() != C:
         raise ValueError(f"{who}: gates must hold {C} values, got {tuple(gates.shape)}")
     yx = torch.as_tensor(yx, dtype=torch.int64).reshape(-1, 2)
@@ -180,19 +148,14 @@ def viewer_frame(features: torch.Tensor, rgb: torch.Tensor, *, proj: torch.Tenso
     without queries.  out: an (H, W, 3) float32 contiguous tensor to write the frame into."""
     from . import _lib
     who = "viewer_frame"
-    _f32(who, "features", features)
+    f32(who, "features", features)
     if features.dim() != 3:
         raise ValueError(f"{who}: features must be (C, H, W), got {tuple(features.shape)}")
-    C, H, W = (int(v) for v in features.shape)
-    N = H * W
-    if not 1 <= C <= MAX_CHANNELS:
-        raise ValueError(f"{who}: need 1 <= C <= {MAX_CHANNELS} channels, got {C}")
-    if not 1 <= N < 1 << 31:
-        raise ValueError(f"{who}: need 1 <= N < 2^31 rows, got {N}")
-    _f32(who, "rgb", rgb)
+    _, C, N, (H, W) = feature_table(who, features)
+    f32(who, "rgb", rgb)
     if tuple(rgb.shape) != (3, H, W):
         raise ValueError(f"{who}: rgb must be (3, {H}, {W}), got {tuple(rgb.shape)}")
-    _f32(who, "cluster_rgb", cluster_rgb, optional=True)
+    f32(who, "cluster_rgb", cluster_rgb, optional=True)
     if cluster_rgb is not None and tuple(cluster_rgb.shape) != (3, H, W):
         raise ValueError(f"{who}: cluster_rgb must be (3, {H}, {W}), got {tuple(cluster_rgb.shape)}")
     if isinstance(modes, str):
@@ -203,40 +166,23 @@ def viewer_frame(features: torch.Tensor, rgb: torch.Tensor, *, proj: torch.Tenso
             raise ValueError(f"{who}: unknown mode {m!r}; modes are {sorted(VIEW_MODES)}")
         bits |= VIEW_MODES[m]
     bits = bits or VIEW_MODES["rgb"]
-    _f32(who, "proj", proj, optional=True)
+    f32(who, "proj", proj, optional=True)
     if proj is not None and tuple(proj.shape) != (C, 3):
         raise ValueError(f"{who}: proj must be ({C}, 3), got {tuple(proj.shape)}")
     if proj is None and bits & VIEW_MODES["pca"]:
         raise ValueError(f"{who}: the \"pca\" mode needs proj ({C}, 3)")
     Q = 0
     if queries is not None:
-        _f32(who, "queries", queries)
-        if queries.dim() == 1:
-            queries = queries[None]
-        if queries.dim() != 2 or queries.shape[1] != C:
-            raise ValueError(f"{who}: queries must be (Q, {C}) or ({C},), got {tuple(queries.shape)}")
-        Q = int(queries.shape[0])
-        if not 1 <= Q <= MAX_QUERIES:
-            raise ValueError(f"{who}: need 1 <= queries <= {MAX_QUERIES}, got {Q}")
-    _f32(who, "gates", gates, optional=True)
-    if gates is not None:
-        if gates.numel() != C or gates.dim() > 2:
-            raise ValueError(f"{who}: gates must hold {C} values, got {tuple(gates.shape)}")
-        gates = gates.reshape(C)
-    try:
-        threshold = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: threshold must be a number, got {threshold!r}") from None
-    if threshold != threshold:
-        raise ValueError(f"{who}: threshold is NaN")
+        queries, Q = query_rows(who, queries, C, MAX_QUERIES)
+    gates = gate_row(who, gates, C)
+    threshold = number(who, "threshold", threshold)
     if out is not None:
-        _f32(who, "out", out)
+        f32(who, "out", out)
         if tuple(out.shape) != (H, W, 3) or not out.is_contiguous():
             raise ValueError(f"{who}: out must be a contiguous ({H}, {W}, 3) tensor, got {tuple(out.shape)}")
     tensors = [("features", features), ("rgb", rgb)] + [(k, t) for k, t in (("cluster_rgb", cluster_rgb), ("proj", proj),
                ("queries", queries), ("gates", gates), ("out", out)) if t is not None]
-    _no_grad_same_gpu(who, tensors)
-    dev = features.device
+    dev = no_grad_one_gpu(who, tensors, "features")
     features, rgb = features.detach().contiguous(), rgb.detach().contiguous()
     cluster_rgb, proj, queries, gates = (None if t is None else t.detach().contiguous() for t in (cluster_rgb, proj, queries, gates))
     if not bits & VIEW_MODES["pca"]:

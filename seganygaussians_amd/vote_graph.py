@@ -15,10 +15,11 @@ from __future__ import annotations
 
 import torch
 
+from ._args import f32, no_grad_one_gpu, number, size_hw
 from ._ffi import check, stream_ptr
 from .clustering import MAX_POINTS, MAX_WORDS
 from .contrastive_loss import MAX_MASKS, PackedSamMasks
-from .mask_scales import _as_packed, _erode, _min_sum, _size
+from .mask_scales import as_packed, erode
 
 MAX_CHANNELS = 256
 MAX_ANCHORS = 32 * MAX_WORDS
@@ -27,26 +28,10 @@ MAX_PROMPTS = 16
 
 
 def _f32_matrix(who: str, name: str, t, rows=None, cols=None) -> None:
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"{who}: {name} must be a float32 tensor, got {getattr(t, 'dtype', type(t))}")
+    f32(who, name, t)
     if t.dim() != 2 or (rows is not None and t.shape[0] != rows) or (cols is not None and t.shape[1] != cols):
         want = f"({'rows' if rows is None else rows}, {'cols' if cols is None else cols})"
         raise ValueError(f"{who}: {name} must be {want}, got {tuple(t.shape)}")
-
-
-def _no_grad_on_gpu(who: str, tensors, dev=None):
-    """Refuses tensors that require grad (while grad mode is on), that are not on a GPU, or that are on different GPUs."""
-    if torch.is_grad_enabled():
-        for name, t in tensors:
-            if t.requires_grad:
-                raise ValueError(f"{who}: {name} requires grad and there is no backward; call under torch.no_grad() or detach it")
-    for name, t in tensors:
-        if not t.is_cuda:
-            raise ValueError(f"{who}: {name} must be on a GPU, got {t.device} (there is no CPU fallback)")
-        dev = t.device if dev is None else dev
-        if t.device != dev:
-            raise ValueError(f"{who}: {name} is on {t.device}, expected {dev}")
-    return dev
 
 
 def sam_mask_features(rendered: torch.Tensor, masks, gates: torch.Tensor, size=None, min_sum: float = 2.0, return_counts: bool = False):
@@ -63,8 +48,7 @@ def sam_mask_features(rendered: torch.Tensor, masks, gates: torch.Tensor, size=N
     same bits on any stream."""
     from . import _lib
     who = "sam_mask_features"
-    if not isinstance(rendered, torch.Tensor) or rendered.dtype != torch.float32:
-        raise ValueError(f"{who}: rendered must be a float32 tensor, got {getattr(rendered, 'dtype', type(rendered))}")
+    f32(who, "rendered", rendered)
     if rendered.dim() != 3:
         raise ValueError(f"{who}: rendered must be (C, H, W), got {tuple(rendered.shape)}")
     C, H, W = (int(v) for v in rendered.shape)
@@ -72,10 +56,10 @@ def sam_mask_features(rendered: torch.Tensor, masks, gates: torch.Tensor, size=N
         raise ValueError(f"{who}: need 1 <= C <= {MAX_CHANNELS} channels, got {C}")
     if H < 1 or W < 1 or C * H * W >= 1 << 31:
         raise ValueError(f"{who}: need a non-empty render of fewer than 2^31 values, got {(C, H, W)}")
-    h, w = _size((H // 4, W // 4) if size is None else size, who)
+    h, w = size_hw(who, (H // 4, W // 4) if size is None else size)
     if C * h * w >= 1 << 31:
         raise ValueError(f"{who}: more than 2^31 values at the working resolution {(h, w)}")
-    min_sum = _min_sum(min_sum, who)
+    min_sum = number(who, "min_sum", min_sum)
     if isinstance(masks, PackedSamMasks):
         M = int(masks.shape[0])
     elif isinstance(masks, torch.Tensor) and masks.dtype == torch.bool and masks.dim() == 3:
@@ -86,14 +70,14 @@ def sam_mask_features(rendered: torch.Tensor, masks, gates: torch.Tensor, size=N
     if not 1 <= M <= MAX_MASKS:
         raise ValueError(f"{who}: need 1 <= M <= {MAX_MASKS} masks, got {M}")
     _f32_matrix(who, "gates", gates, M, C)
-    dev = _no_grad_on_gpu(who, [("rendered", rendered), ("gates", gates)])
-    packed = _as_packed(masks, dev, who)
+    dev = no_grad_one_gpu(who, [("rendered", rendered), ("gates", gates)])
+    packed = as_packed(who, masks, dev)
     if M * h * ((w + 63) // 64) >= 1 << 31:
         raise ValueError(f"{who}: more than 2^31 mask words")
     L = _lib.load()
     rendered, gates = rendered.detach().contiguous(), gates.detach().contiguous()
     with torch.cuda.device(dev):
-        eroded = _erode(packed, h, w, min_sum)
+        eroded = erode(packed, h, w, min_sum)
         nbytes = int(L.mi_vote_mask_features_workspace_bytes(M, C, h, w))
         ws = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.int64)
         out = torch.empty((M, C), device=dev, dtype=torch.float32)
@@ -125,12 +109,7 @@ def anchor_bits(mask_features: torch.Tensor, gates: torch.Tensor, anchor_feature
     A = int(anchor_features.shape[0])
     if not 1 <= A <= MAX_ANCHORS:
         raise ValueError(f"{who}: need 1 <= A <= {MAX_ANCHORS} anchors, got {A}")
-    try:
-        threshold = float(threshold)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: threshold must be a number, got {threshold!r}") from None
-    if threshold != threshold:
-        raise ValueError(f"{who}: threshold is NaN")
+    threshold = number(who, "threshold", threshold)
     words = (A + 31) // 32
     if not isinstance(row_offset, int) or isinstance(row_offset, bool):
         raise ValueError(f"{who}: row_offset must be an integer, got {row_offset!r}")
@@ -149,7 +128,7 @@ def anchor_bits(mask_features: torch.Tensor, gates: torch.Tensor, anchor_feature
         if not 0 <= row_offset <= out.shape[0] - M:
             raise ValueError(f"{who}: rows {row_offset} .. {row_offset + M - 1} do not lie in out's {out.shape[0]} rows")
         tensors.append(("out", out))
-    dev = _no_grad_on_gpu(who, tensors)
+    dev = no_grad_one_gpu(who, tensors)
     L = _lib.load()
     phi, gates, anchors = mask_features.detach().contiguous(), gates.detach().contiguous(), anchor_features.detach().contiguous()
     with torch.cuda.device(dev):
@@ -182,7 +161,7 @@ def clip_relevancy(embeds: torch.Tensor, pos_embeds: torch.Tensor, neg_embeds: t
     P, Q = int(pos_embeds.shape[0]), int(neg_embeds.shape[0])
     if not (1 <= P <= MAX_PROMPTS and 1 <= Q <= MAX_PROMPTS):
         raise ValueError(f"{who}: need 1 <= P, Q <= {MAX_PROMPTS} prompt embeddings, got P = {P}, Q = {Q}")
-    dev = _no_grad_on_gpu(who, [("embeds", embeds), ("pos_embeds", pos_embeds), ("neg_embeds", neg_embeds)])
+    dev = no_grad_one_gpu(who, [("embeds", embeds), ("pos_embeds", pos_embeds), ("neg_embeds", neg_embeds)])
     L = _lib.load()
     embeds, pos, neg = embeds.detach().contiguous(), pos_embeds.detach().contiguous(), neg_embeds.detach().contiguous()
     out = torch.empty((N, P), device=dev, dtype=torch.float32)

@@ -154,10 +154,31 @@ def test_one_set_of_call_helpers():
     shared = {name: fn for name, fn in vars(_ffi).items() if isinstance(fn, types.FunctionType)}
     assert set(shared) == {"check", "ptr", "dev_ptr", "contig", "stream_ptr"}
     for name in ("knn", "contrastive_loss", "contrastive_frontend", "segmentation", "photometric", "mask_scales", "knn_smooth",
-                 "rasterizer", "geometry_cache"):
+                 "rasterizer", "geometry_cache", "sam_masks", "clip_tiles", "viewer", "vote_graph", "clustering", "lifting",
+                 "training_step"):
         mod = importlib.import_module("seganygaussians_amd." + name)
         for attr, value in vars(mod).items():
             assert attr not in ("_check", "_ptr", "_stream", "_stream_ptr", "_dev_ptr", "_contig"), f"{name}.{attr}"
             if attr in shared:
                 assert value is shared[attr], f"{name}.{attr} is a copy"
         assert any(vars(mod).get(k) is fn for k, fn in shared.items()), f"{name} does not use _ffi"
+
+
+def test_one_set_of_argument_checks():
+    """The feature modules take the argument checks they share from _args.py (which loads nothing of the package), and the
+    private helpers a module has are its own: none is imported from a sibling, and none is a copy of a shared check."""
+    import importlib
+    import types
+    from seganygaussians_amd import _args
+    shared = {name for name, fn in vars(_args).items() if isinstance(fn, types.FunctionType)}
+    assert shared == {"to_float", "number", "f32", "size_hw", "no_grad_one_gpu", "check_out"}
+    assert not any(isinstance(v, types.ModuleType) and v.__name__.startswith("seganygaussians_amd") for v in vars(_args).values())
+    for name in ("segmentation", "photometric", "mask_scales", "clustering", "lifting", "vote_graph", "knn_smooth", "sam_masks",
+                 "clip_tiles", "viewer"):
+        mod = importlib.import_module("seganygaussians_amd." + name)
+        for attr, value in vars(mod).items():
+            if attr.startswith("_") and isinstance(value, types.FunctionType):
+                assert value.__module__ == mod.__name__, f"{name}.{attr} comes from {value.__module__}"
+                assert attr not in ("_f32", "_threshold", "_min_sum", "_no_grad_same_gpu", "_no_grad_on_gpu"), f"{name}.{attr}"
+            if attr in shared and isinstance(value, types.FunctionType):
+                assert value is getattr(_args, attr), f"{name}.{attr} is a copy"
