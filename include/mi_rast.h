@@ -336,6 +336,7 @@ int mi_rast_profile_read(float* ms /* [MI_STAGE_COUNT] */);
  *     m += (g - m) (1 - beta1);   v = beta2 v + (1 - beta2) g g;   p -= step_size m / (sqrt(v) inv_sqrt_bc2 + eps)
  * (1 - beta) is formed in double and rounded once.  No weight decay, no amsgrad.  16-byte accesses where p, g, m and v share
  * their offset modulo 16, single floats before and after that body (and throughout where they do not). */
+#define MI_TRAIN_ADAM_MAX_TENSORS 16
 int mi_train_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                        float* const* exp_avg_sq, const size_t* counts, const double* step_sizes, double inv_sqrt_bc2,
                        double beta1, double beta2, double eps, void* stream);
@@ -369,6 +370,7 @@ int mi_train_densify_counts(int P, const void* workspace, size_t workspace_bytes
  * source row for kept originals and 0 for every new row.  Exactly one XYZ, one SCALING and one ROTATION tensor.
  * counts: the host ints the counts call returned for this workspace. */
 enum { MI_TRAIN_COPY = 0, MI_TRAIN_MOMENT = 1, MI_TRAIN_XYZ = 2, MI_TRAIN_SCALING = 3, MI_TRAIN_ROTATION = 4 };
+#define MI_TRAIN_DENSIFY_MAX_TENSORS 32
 int mi_train_densify_apply(int P, const int* counts, int n_tensors, const float* const* src, float* const* dst, const int* cols,
                            const int* kinds, const float* samples, const void* workspace, size_t workspace_bytes, void* stream);
 

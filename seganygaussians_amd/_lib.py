@@ -1,76 +1,132 @@
-"""ctypes binding of the C-ABI library (include/mi_rast.h).  Fails loudly when the HIP extension is
-missing: there is NO CPU / PyTorch fallback in the product path."""
+"""ctypes binding of the C-ABI library, read off its headers (include/*.h): what they declare is what is bound, and every MI_*
+constant they define is an attribute of this module.  Fails loudly when the HIP extension is missing: there is NO CPU / PyTorch
+fallback in the product path."""
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
-from .build import LIB_PATH
+from .build import HEADERS, LIB_PATH
 
 RESIZE_FN = C.CFUNCTYPE(C.c_void_p, C.c_size_t, C.c_void_p)
-
-MI_GEOM_FIELDS = ["depths", "means2D", "conic_opacity", "cov3D", "rgb", "clamped", "tiles_touched",
-                  "depth_key", "index_rec", "cull_counter", "band_bits", "bwd_pack"]
-MI_IMG_FIELDS = ["final_T", "n_contrib", "ranges", "tile_consumed", "tile_count", "tile_cursor", "num_rendered", "tile_nsurv"]
-MI_BIN_FIELDS = ["entries", "scratch", "blend_list"]
-MI_RAST_FULL_LISTS, MI_RAST_F32_BLEND, MI_RAST_NO_CULL, MI_RAST_FAST_EXP, MI_RAST_VERIFY_LISTS, MI_RAST_TILE_FWD = 1, 2, 4, 8, 16, 32   # `flags` of mi_rast_forward (include/mi_rast.h)
-MI_RAST_PREZERO_BWD = 64   # forward + the one backward of that forward (include/mi_rast.h)
-MI_RAST_EXACT_EXP = 128    # forward blend with expf for every pair instead of the hybrid form (include/mi_rast.h)
-MI_RAST_EQUAL_RUNS = 256   # A/B aid: XCD runs of equal tile counts in both blend kernels instead of equal modelled work (include/mi_rast.h)
-MI_RAST_BWD_FEATURES_ONLY = 512   # mi_rast_backward: dL_dcolor alone (extension, include/mi_rast.h)
-MI_STAGES = ["preprocess", "tile_scan", "emit", "tile_sort", "blend_fwd", "blend_bwd", "geom_bwd"]
-
-# include/mi_segment.h, its clustering section (csrc/mi_cluster.hip); listed on its own and as the tail of EXPORTS
-CLUSTER_EXPORTS = ["mi_cluster_workspace_bytes", "mi_cluster_core_distances", "mi_cluster_mst", "mi_cluster_mst_rounds", "mi_cluster_labels_host"]
-# include/mi_rast.h, its score-lifting section (csrc/lift.h); listed on its own and as the tail of EXPORTS
-LIFT_EXPORTS = ["mi_rast_lift", "mi_rast_lift_reuse"]
-MI_RAST_LIFT_MAX_CHANNELS = 64
-# include/mi_segment.h, its vote-graph section (csrc/mi_vote_graph.hip); listed on its own and as the tail of EXPORTS
-VOTE_GRAPH_EXPORTS = ["mi_vote_mask_features_workspace_bytes", "mi_vote_mask_features", "mi_vote_anchor_bits", "mi_vote_relevancy"]
-# include/mi_segment.h, its viewer-frame section (csrc/mi_viewer.hip); listed on its own and as the tail of EXPORTS
-VIEWER_EXPORTS = ["mi_view_moments_workspace_bytes", "mi_view_moments_block", "mi_view_moments", "mi_view_frame"]
-MI_VIEW_MODES = {"rgb": 1, "pca": 2, "cluster": 4, "similarity": 8}
-EXPORTS = [
-    "mi_rast_forward", "mi_rast_forward_reuse", "mi_rast_last_longest_run", "mi_rast_fingerprint", "mi_rast_features_only_supported", "mi_rast_backward", "mi_rast_mark_visible", "mi_rast_mask_forward",
-    "mi_rast_mask_backward", "mi_rast_last_error", "mi_rast_version", "mi_rast_supported_channels",
-    "mi_rast_get_higher_msb", "mi_rast_geometry_layout", "mi_rast_image_layout", "mi_rast_binning_layout",
-    "mi_rast_profile_enable", "mi_rast_profile_read",
-    "mi_knn_smooth_forward", "mi_knn_smooth_backward", "mi_knn_smooth_multi_forward", "mi_knn_smooth_multi_backward",  # include/mi_knn_smooth.h
-    "mi_knn_workspace_bytes", "mi_knn_build", "mi_knn_query", "mi_knn_mean_dist2",  # include/mi_knn.h
-    "mi_contrastive_forward", "mi_contrastive_backward",  # include/mi_contrastive.h
-    "mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
-    "mi_contrastive_loss_backward",  # include/mi_contrastive.h: the loss itself
-] + CLUSTER_EXPORTS + LIFT_EXPORTS + VOTE_GRAPH_EXPORTS + VIEWER_EXPORTS
-# include/mi_mask_scales.h, its mask-sets section (csrc/mi_mask_sets.hip); listed on its own and as the tail of MASK_SCALES_EXPORTS
-MASK_SETS_EXPORTS = ["mi_mask_overlaps", "mi_mask_boxes", "mi_mask_nms_keep", "mi_mask_score_images"]
-MI_MASK_SCORE_MODE = {"sum": 0, "mean": 1, "max": 2}
-MI_MASK_SCORE_MAX_COLUMNS = 64
-# include/mi_mask_scales.h, its CLIP-tiles section (csrc/mi_clip_tiles.hip; mi_mask_resize in csrc/mi_mask_scales.hip)
-CLIP_TILES_EXPORTS = ["mi_mask_resize", "mi_mask_clip_tiles", "mi_mask_index_map"]
-MI_CLIP_TILES_LAYOUT = {"crop": 0, "pad_square": 1}
-MI_CLIP_TILES_MAX_SIZE, MI_CLIP_TILES_MAX_SIDE = 512, 32768
-MASK_SCALES_EXPORTS = ["mi_mask_scales_workspace_bytes", "mi_mask_erode", "mi_mask_erode_min_sum", "mi_mask_scales"] + MASK_SETS_EXPORTS + CLIP_TILES_EXPORTS   # include/mi_mask_scales.h
-MI_VOTE_MAX_ANCHORS, MI_VOTE_MAX_EMBED_DIM, MI_VOTE_MAX_PROMPTS = 32768, 1024, 16
-SEGMENT_EXPORTS = ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]   # include/mi_segment.h
-MI_SEGMENT_IMAGE, MI_SEGMENT_POINTS = 0, 1
-PHOTOMETRIC_EXPORTS = ["mi_photo_loss_workspace_bytes", "mi_photo_loss_window", "mi_photo_loss_forward", "mi_photo_loss_backward"]   # include/mi_photometric.h
-MI_PHOTO_L1, MI_PHOTO_SSIM = 1, 2
-# include/mi_rast.h, its training-step section (csrc/mi_train_step.hip)
-TRAIN_STEP_EXPORTS = ["mi_train_adam_step", "mi_train_densify_stats", "mi_train_densify_workspace_bytes", "mi_train_densify_plan",
-                      "mi_train_densify_counts", "mi_train_densify_apply"]
-MI_TRAIN_COUNTS = ["clones", "splits", "kept_originals", "kept_clones", "kept_children"]
-MI_TRAIN_COPY, MI_TRAIN_MOMENT, MI_TRAIN_XYZ, MI_TRAIN_SCALING, MI_TRAIN_ROTATION = 0, 1, 2, 3, 4
-MI_TRAIN_ADAM_MAX_TENSORS, MI_TRAIN_DENSIFY_MAX_TENSORS = 16, 32
-MI_CLUSTER_METRIC = {"euclidean": 0, "jaccard": 1}
-MI_CLUSTER_MAX_POINTS, MI_CLUSTER_MAX_CHANNELS, MI_CLUSTER_MAX_WORDS, MI_CLUSTER_MAX_CORE_K = 1 << 20, 256, 1024, 64
-ALL_EXPORTS = EXPORTS + MASK_SCALES_EXPORTS + SEGMENT_EXPORTS + PHOTOMETRIC_EXPORTS + TRAIN_STEP_EXPORTS   # every function the headers in include/ declare
-MI_SEGMENT_PRE = {"none": 0, "l2": 1, "eps": 2}
-
-_lib = None
 
 
 class MiRastError(RuntimeError):
     pass
+
+
+# ---- the grammar the headers keep; anything else is refused, never guessed ----
+_SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "uint32_t": C.c_uint32}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char*": C.c_char_p})
+_RESIZE_TYPEDEF = "typedef char* (*mi_rast_resize_fn)(size_t nbytes, void* user)"
+_DIRECTIVES = re.compile(r"#\s*(include\b|ifndef\b|ifdef\s+__cplusplus$|endif$)")
+_INT = r"(0|[1-9][0-9]*|0[xX][0-9a-fA-F]+)"
+
+
+def _integer(text):
+    """The value of a decimal or hex literal or of `(a << b)`; None for anything else."""
+    m = re.fullmatch(rf"{_INT}|\(\s*{_INT}\s*<<\s*{_INT}\s*\)", text)
+    return None if not m else int(m.group(1), 0) if m.group(1) else int(m.group(2), 0) << int(m.group(3), 0)
+
+
+def _ctype(text):
+    return re.sub(r"\s*\*\s*", "*", " ".join(text.split()))
+
+
+def parse_header(text: str, header: str = "<header>"):
+    """One header's text -> ([(function, restype, [argtypes])] in declaration order, {MI_* constant: value})."""
+    def refuse(why, decl):
+        raise MiRastError(f"{header}: {why}: {' '.join(decl.split())!r}")
+
+    functions, constants, code, in_cplusplus = [], {}, [], False
+    for line in re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).split("\n"):
+        line = line.strip()
+        if not line.startswith("#"):
+            if not in_cplusplus:     # an `#ifdef __cplusplus` block holds extern "C" { or its }
+                code.append(line)
+            continue
+        m = re.fullmatch(r"#\s*define\s+(\w+)\s*(.*)", line)
+        if m and m.group(2) and m.group(1).startswith("MI_"):     # a define without a value is an include guard
+            value = _integer(m.group(2))
+            if value is None or m.group(1) in constants:
+                refuse("a define whose value is not an integer, or defined twice", line)
+            constants[m.group(1)] = value
+        elif not m and not _DIRECTIVES.match(line):
+            refuse("an unknown directive", line)
+        in_cplusplus = line.endswith("__cplusplus") or in_cplusplus and not line.endswith("endif")     # from its #ifdef to the next #endif
+    for decl in " ".join(code).split(";"):
+        decl = decl.strip()
+        if not decl or " ".join(decl.split()) == _RESIZE_TYPEDEF:
+            continue
+        m = re.fullmatch(r"enum\s*\{([^{}]*)\}", decl)
+        if m:
+            value = -1
+            for item in m.group(1).split(","):
+                e = re.fullmatch(r"\s*(MI_\w+)\s*(?:=\s*(\S+)\s*)?", item)
+                if e:
+                    value = value + 1 if e.group(2) is None else _integer(e.group(2))
+                if not e or value is None or e.group(1) in constants:
+                    refuse("an enumerator that is not `MI_NAME` or `MI_NAME = integer`, or defined twice", decl)
+                constants[e.group(1)] = value
+            continue
+        m = re.fullmatch(r"([\w\s*]+?)\b(\w+)\s*\(([^()]*)\)", decl)
+        if not m or _ctype(m.group(1)) not in _RETURNS:
+            refuse("not `ret name(params)` with a known return type, an anonymous enum or the resize callback's typedef", decl)
+        argtypes = []
+        for param in [] if m.group(3).strip() == "void" else m.group(3).split(","):
+            p = re.fullmatch(r"\s*([\w\s*]+?)\b(\w+)\s*", param)
+            if not p:
+                refuse(f"parameter {param.strip()!r} is not `type name`", decl)
+            t = _ctype(p.group(1))
+            if "*" not in t and t != "mi_rast_resize_fn" and t not in _SCALARS:
+                refuse(f"unknown type {t!r} of parameter {p.group(2)!r}", decl)
+            argtypes.append(C.c_void_p if "*" in t else RESIZE_FN if t == "mi_rast_resize_fn" else _SCALARS[t])
+        functions.append((m.group(2), _RETURNS[_ctype(m.group(1))], argtypes))
+    return functions, constants
+
+
+DECLARED = {}      # header base name -> its functions in declaration order
+SIGNATURES = {}    # function -> (restype, [argtypes])
+CONSTANTS = {}     # every MI_* define with an integer value and every enumerator
+for _path in HEADERS:
+    _header = os.path.basename(_path)
+    with open(_path) as _f:
+        _functions, _constants = parse_header(_f.read(), _header)
+    DECLARED[_header] = [n for n, _, _ in _functions]
+    _again = sorted(set(DECLARED[_header]) & set(SIGNATURES) | set(_constants) & set(CONSTANTS))
+    if _again or len(set(DECLARED[_header])) != len(_functions):
+        raise MiRastError(f"{_header}: declared twice: {_again or DECLARED[_header]}")
+    SIGNATURES.update((n, (r, a)) for n, r, a in _functions)
+    CONSTANTS.update(_constants)
+globals().update(CONSTANTS)     # _lib.MI_RAST_FULL_LISTS, _lib.MI_SEGMENT_MAX_CHANNELS, ...
+ALL_EXPORTS = [n for names in DECLARED.values() for n in names]   # every function the headers in include/ declare
+
+
+def _named(prefix, *names):
+    return {n: CONSTANTS[prefix + n.upper()] for n in names}
+
+
+MI_VIEW_MODES = _named("MI_VIEW_", "rgb", "pca", "cluster", "similarity")
+MI_MASK_SCORE_MODE = _named("MI_MASK_SCORE_", "sum", "mean", "max")
+MI_CLIP_TILES_LAYOUT = _named("MI_CLIP_TILES_", "crop", "pad_square")
+MI_CLUSTER_METRIC = _named("MI_CLUSTER_", "euclidean", "jaccard")
+MI_SEGMENT_PRE = _named("MI_SEGMENT_PRE_", "none", "l2", "eps")
+
+# the fields of the layout, profile and count tables in the order of their enums: written out, for their case is not the enumerators'
+MI_GEOM_FIELDS = ["depths", "means2D", "conic_opacity", "cov3D", "rgb", "clamped", "tiles_touched",
+                  "depth_key", "index_rec", "cull_counter", "band_bits", "bwd_pack"]
+MI_IMG_FIELDS = ["final_T", "n_contrib", "ranges", "tile_consumed", "tile_count", "tile_cursor", "num_rendered", "tile_nsurv"]
+MI_BIN_FIELDS = ["entries", "scratch", "blend_list"]
+MI_STAGES = ["preprocess", "tile_scan", "emit", "tile_sort", "blend_fwd", "blend_bwd", "geom_bwd"]
+MI_TRAIN_COUNTS = ["clones", "splits", "kept_originals", "kept_clones", "kept_children"]
+for _fields, _prefix, _count in ((MI_GEOM_FIELDS, "MI_GEOM_", "MI_GEOM_NFIELDS"), (MI_IMG_FIELDS, "MI_IMG_", "MI_IMG_NFIELDS"),
+                                 (MI_BIN_FIELDS, "MI_BIN_", "MI_BIN_NFIELDS"), (MI_STAGES, "MI_STAGE_", "MI_STAGE_COUNT"),
+                                 (MI_TRAIN_COUNTS, "MI_TRAIN_", "MI_TRAIN_NCOUNTS")):
+    if [CONSTANTS.get(_prefix + n.upper()) for n in _fields] != list(range(CONSTANTS[_count])):
+        raise MiRastError(f"{_fields} are not the {_count} = {CONSTANTS[_count]} enumerators {_prefix}* of the headers, in order")
+
+_lib = None
 
 
 def load():
@@ -90,158 +146,9 @@ def load():
         L = C.CDLL(lib_path)
     except OSError as e:  # e.g. libamdhip64 missing
         raise MiRastError(f"cannot load {lib_path}: {e}") from e
-    vp, i, f = C.c_void_p, C.c_int, C.c_float
-    L.mi_rast_forward.restype = i
-    L.mi_rast_forward.argtypes = [RESIZE_FN, vp, RESIZE_FN, vp, RESIZE_FN, vp, i, i, i, i, vp, i, i,
-                                  vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f, i,
-                                  vp, vp, vp, vp, vp, i, i, vp, vp, vp, C.POINTER(i)]
-    L.mi_rast_forward_reuse.restype = i
-    L.mi_rast_forward_reuse.argtypes = [i, i, i, vp, i, i, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, vp, i, vp, vp, vp]
-    L.mi_rast_fingerprint.restype = i
-    L.mi_rast_fingerprint.argtypes = [i, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64), vp]
-    L.mi_rast_last_longest_run.restype = i
-    L.mi_rast_last_longest_run.argtypes = []
-    L.mi_rast_features_only_supported.restype = i
-    L.mi_rast_features_only_supported.argtypes = [i]
-    L.mi_rast_backward.restype = i
-    L.mi_rast_backward.argtypes = [i, i, i, i, i, vp, i, i, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, f, f,
-                                   vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, i, vp]
-    L.mi_rast_mark_visible.restype = i
-    L.mi_rast_mark_visible.argtypes = [i, vp, vp, vp, vp, vp]
-    L.mi_rast_mask_forward.restype = i
-    L.mi_rast_mask_forward.argtypes = [RESIZE_FN, vp, RESIZE_FN, vp, RESIZE_FN, vp, i, i, i, vp, vp, vp, vp, f,
-                                       vp, vp, vp, vp, f, f, i, vp, vp, i, i, vp, C.POINTER(i)]
-    L.mi_rast_mask_backward.restype = i
-    L.mi_rast_mask_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, i, i, vp]
-    L.mi_rast_lift.restype = i
-    L.mi_rast_lift.argtypes = [RESIZE_FN, vp, RESIZE_FN, vp, RESIZE_FN, vp, i, i, i, i, vp, vp, vp, f, vp, vp, vp, vp, f, f, i,
-                               vp, vp, vp, i, i, vp, C.POINTER(i)]
-    L.mi_rast_lift_reuse.restype = i
-    L.mi_rast_lift_reuse.argtypes = [i, i, i, i, i, vp, vp, vp, vp, vp, i, vp]
-    L.mi_rast_last_error.restype = C.c_char_p
-    L.mi_rast_version.restype = C.c_char_p
-    L.mi_rast_supported_channels.restype = i
-    L.mi_rast_supported_channels.argtypes = [C.POINTER(i), i]
-    L.mi_rast_get_higher_msb.restype = C.c_uint32
-    L.mi_rast_get_higher_msb.argtypes = [C.c_uint32]
-    for name, n in (("mi_rast_geometry_layout", 1), ("mi_rast_binning_layout", 1)):
+    for name, (restype, argtypes) in SIGNATURES.items():
         fn = getattr(L, name)
-        fn.restype = C.c_size_t
-        fn.argtypes = [i, C.POINTER(C.c_size_t)]
-    L.mi_rast_image_layout.restype = C.c_size_t
-    L.mi_rast_image_layout.argtypes = [i, i, C.POINTER(C.c_size_t)]
-    L.mi_rast_profile_enable.restype = i
-    L.mi_rast_profile_enable.argtypes = [i]
-    L.mi_rast_profile_read.restype = i
-    L.mi_rast_profile_read.argtypes = [C.POINTER(f)]
-    u32 = C.c_uint32
-    L.mi_knn_smooth_forward.restype = i
-    L.mi_knn_smooth_forward.argtypes = [i, i, i, vp, u32, vp, vp, i, vp]
-    L.mi_knn_smooth_backward.restype = i
-    L.mi_knn_smooth_backward.argtypes = [i, i, i, vp, vp, vp, u32, vp, vp, vp, vp, i, vp]
-    L.mi_knn_smooth_multi_forward.restype = i
-    L.mi_knn_smooth_multi_forward.argtypes = [i, i, i, C.POINTER(i), vp, vp, i, vp, vp, i, vp]
-    L.mi_knn_smooth_multi_backward.restype = i
-    L.mi_knn_smooth_multi_backward.argtypes = [i, i, i, C.POINTER(i), vp, vp, vp, vp, i, vp, vp, vp, vp, vp, i, vp]
-    L.mi_knn_workspace_bytes.restype = C.c_size_t
-    L.mi_knn_workspace_bytes.argtypes = [i]
-    L.mi_knn_build.restype = i
-    L.mi_knn_build.argtypes = [i, vp, vp, C.c_size_t, vp]
-    L.mi_knn_query.restype = i
-    L.mi_knn_query.argtypes = [i, vp, i, vp, i, i, vp, vp, vp]
-    L.mi_knn_mean_dist2.restype = i
-    L.mi_knn_mean_dist2.argtypes = [i, vp, vp, C.c_size_t, vp, vp]
-    L.mi_contrastive_forward.restype = i
-    L.mi_contrastive_forward.argtypes = [i, i, i, vp, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp]
-    L.mi_contrastive_backward.restype = i
-    L.mi_contrastive_backward.argtypes = [i, i, i, vp, i, i, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mi_contrastive_pack_masks.restype = i
-    L.mi_contrastive_pack_masks.argtypes = [i, i, i, vp, vp, vp]
-    L.mi_contrastive_cover.restype = i
-    L.mi_contrastive_cover.argtypes = [i, i, i, vp, vp, f, vp, vp, vp]
-    L.mi_contrastive_targets.restype = i
-    L.mi_contrastive_targets.argtypes = [i, i, i, vp, vp, i, vp, i, vp, vp, vp, vp, vp, vp]
-    L.mi_contrastive_loss_forward.restype = i
-    L.mi_contrastive_loss_forward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mi_contrastive_loss_backward.restype = i
-    L.mi_contrastive_loss_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.mi_mask_scales_workspace_bytes.restype = C.c_size_t
-    L.mi_mask_scales_workspace_bytes.argtypes = [i, i, i]
-    L.mi_mask_erode.restype = i
-    L.mi_mask_erode.argtypes = [i, i, i, vp, i, i, vp, vp]
-    L.mi_mask_erode_min_sum.restype = i
-    L.mi_mask_erode_min_sum.argtypes = [i, i, i, vp, i, i, f, vp, vp]
-    L.mi_mask_scales.restype = i
-    L.mi_mask_scales.argtypes = [i, i, i, vp, vp, C.c_double, C.c_double, vp, C.c_size_t, vp, vp, vp]
-    L.mi_mask_overlaps.restype = i
-    L.mi_mask_overlaps.argtypes = [i, i, i, vp, vp, vp, vp, vp]
-    L.mi_mask_boxes.restype = i
-    L.mi_mask_boxes.argtypes = [i, i, i, vp, vp, vp, vp]
-    L.mi_mask_nms_keep.restype = i
-    L.mi_mask_nms_keep.argtypes = [i, vp, vp, vp, f, f, f, vp, vp]
-    L.mi_mask_score_images.restype = i
-    L.mi_mask_score_images.argtypes = [i, i, i, i, vp, vp, i, vp, vp]
-    L.mi_mask_resize.restype = i
-    L.mi_mask_resize.argtypes = [i, i, i, vp, i, i, f, vp, vp]
-    L.mi_mask_clip_tiles.restype = i
-    L.mi_mask_clip_tiles.argtypes = [i, i, i, vp, vp, vp, i, f, i, C.POINTER(f), C.POINTER(f), i, i, i, vp, vp]
-    L.mi_mask_index_map.restype = i
-    L.mi_mask_index_map.argtypes = [i, i, i, vp, i, vp, vp]
-    L.mi_segment_scores.restype = i
-    L.mi_segment_scores.argtypes = [i, i, i, i, vp, vp, vp, i, i, vp, vp]
-    L.mi_segment_select.restype = i
-    L.mi_segment_select.argtypes = [i, i, i, i, vp, vp, vp, i, i, f, vp, vp, vp]
-    L.mi_segment_assign.restype = i
-    L.mi_segment_assign.argtypes = [i, i, i, i, vp, vp, vp, i, vp, vp, vp]
-    L.mi_segment_assign_block.restype = i
-    L.mi_segment_assign_block.argtypes = [i]
-    L.mi_photo_loss_workspace_bytes.restype = C.c_size_t
-    L.mi_photo_loss_workspace_bytes.argtypes = [i, i, i]
-    L.mi_photo_loss_window.restype = None
-    L.mi_photo_loss_window.argtypes = [C.POINTER(f), C.POINTER(C.c_double)]
-    L.mi_photo_loss_forward.restype = i
-    L.mi_photo_loss_forward.argtypes = [i, i, i, i, vp, vp, C.c_double, i, vp, vp, C.c_size_t, vp, vp]
-    L.mi_photo_loss_backward.restype = i
-    L.mi_photo_loss_backward.argtypes = [i, i, i, i, vp, vp, vp, vp, i, f, f, vp, vp]
-    pp, d = C.POINTER(C.c_void_p), C.c_double
-    L.mi_train_adam_step.restype = i
-    L.mi_train_adam_step.argtypes = [i, pp, pp, pp, pp, C.POINTER(C.c_size_t), C.POINTER(d), d, d, d, d, vp]
-    L.mi_train_densify_stats.restype = i
-    L.mi_train_densify_stats.argtypes = [i, vp, vp, vp, vp, vp, vp]
-    L.mi_train_densify_workspace_bytes.restype = C.c_size_t
-    L.mi_train_densify_workspace_bytes.argtypes = [i]
-    L.mi_train_densify_plan.restype = i
-    L.mi_train_densify_plan.argtypes = [i, vp, vp, vp, vp, d, d, d, d, i, vp, C.c_size_t, vp, vp]
-    L.mi_train_densify_counts.restype = i
-    L.mi_train_densify_counts.argtypes = [i, vp, C.c_size_t, C.POINTER(i), vp]
-    L.mi_train_densify_apply.restype = i
-    L.mi_train_densify_apply.argtypes = [i, C.POINTER(i), i, pp, pp, C.POINTER(i), C.POINTER(i), vp, vp, C.c_size_t, vp]
-    L.mi_cluster_workspace_bytes.restype = C.c_size_t
-    L.mi_cluster_workspace_bytes.argtypes = [i, i, i, i]
-    L.mi_cluster_core_distances.restype = i
-    L.mi_cluster_core_distances.argtypes = [i, i, i, vp, i, vp, vp, C.c_size_t, vp]
-    L.mi_cluster_mst.restype = i
-    L.mi_cluster_mst.argtypes = [i, i, i, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
-    L.mi_cluster_mst_rounds.restype = i
-    L.mi_cluster_mst_rounds.argtypes = []
-    L.mi_cluster_labels_host.restype = i
-    L.mi_cluster_labels_host.argtypes = [i, i, vp, vp, vp, i, d, i, vp, C.POINTER(i)]
-    L.mi_vote_mask_features_workspace_bytes.restype = C.c_size_t
-    L.mi_vote_mask_features_workspace_bytes.argtypes = [i, i, i, i]
-    L.mi_vote_mask_features.restype = i
-    L.mi_vote_mask_features.argtypes = [i, i, i, i, vp, i, i, vp, vp, vp, C.c_size_t, vp, vp, vp]
-    L.mi_vote_anchor_bits.restype = i
-    L.mi_vote_anchor_bits.argtypes = [i, i, i, vp, vp, vp, f, vp, vp, vp]
-    L.mi_vote_relevancy.restype = i
-    L.mi_vote_relevancy.argtypes = [i, i, i, i, vp, i, vp, vp, i, vp, vp]
-    L.mi_view_moments_workspace_bytes.restype = C.c_size_t
-    L.mi_view_moments_workspace_bytes.argtypes = [i, i]
-    L.mi_view_moments_block.restype = i
-    L.mi_view_moments_block.argtypes = []
-    L.mi_view_moments.restype = i
-    L.mi_view_moments.argtypes = [i, i, i, vp, vp, i, i, vp, C.c_size_t, vp, vp, vp]
-    L.mi_view_frame.restype = i
-    L.mi_view_frame.argtypes = [i, i, vp, vp, vp, vp, i, vp, vp, f, i, i, vp, vp, vp, vp]
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

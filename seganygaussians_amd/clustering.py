@@ -19,14 +19,15 @@ import ctypes
 
 import torch
 
+from . import _lib
 from ._args import no_grad_one_gpu, to_float
 from ._ffi import check, stream_ptr
 
-METRICS = {"euclidean": 0, "jaccard": 1}
-MAX_POINTS = 1 << 20
-MAX_CHANNELS = 256
-MAX_WORDS = 1024
-MAX_CORE_K = 64
+METRICS = _lib.MI_CLUSTER_METRIC
+MAX_POINTS = _lib.MI_CLUSTER_MAX_POINTS
+MAX_CHANNELS = _lib.MI_CLUSTER_MAX_CHANNELS
+MAX_WORDS = _lib.MI_CLUSTER_MAX_WORDS
+MAX_CORE_K = _lib.MI_CLUSTER_MAX_CORE_K
 
 
 def pack_bits(bool_matrix: torch.Tensor) -> torch.Tensor:
@@ -108,7 +109,6 @@ def _mst(L, points, mid, n, width, core, ws, nbytes):
 
 def core_distances(points: torch.Tensor, core_k: int, metric: str = "euclidean") -> torch.Tensor:
     """float32 (n,): the core_k-th smallest distance from every row to all rows, itself included."""
-    from . import _lib
     points, mid, n, width = _prepare("core_distances", points, core_k, metric)
     L = _lib.load()
     with torch.cuda.device(points.device):
@@ -119,7 +119,6 @@ def core_distances(points: torch.Tensor, core_k: int, metric: str = "euclidean")
 def mutual_reachability_mst(points: torch.Tensor, core_k: int, metric: str = "euclidean"):
     """(edge_a int32, edge_b int32, edge_w float32), each (n - 1,), on the device: a minimum spanning tree of the complete graph under
     max(core_a, core_b, d(a, b)), a < b.  The same input gives the same edges in the same order."""
-    from . import _lib
     points, mid, n, width = _prepare("mutual_reachability_mst", points, core_k, metric)
     L = _lib.load()
     with torch.cuda.device(points.device):
@@ -132,7 +131,6 @@ def labels_from_mst(edge_a: torch.Tensor, edge_b: torch.Tensor, edge_w: torch.Te
                     cluster_selection_epsilon: float = 0.0, allow_single_cluster: bool = False) -> torch.Tensor:
     """The host half: CPU tensors in (int32, int32, float32, one entry per edge, in any order), int64 labels (n,) out on the CPU.
     Refuses edges that are not a spanning tree of n points.  Needs no GPU."""
-    from . import _lib
     if not isinstance(n, int) or isinstance(n, bool):
         raise ValueError(f"labels_from_mst: n must be an integer, got {n!r}")
     eps = _check_params("labels_from_mst", min_cluster_size, cluster_selection_epsilon, n)
@@ -164,7 +162,6 @@ def hdbscan_labels(points: torch.Tensor, min_cluster_size: int = 10, min_samples
     cluster_in_3D (saga_gui.py:529-531) is hdbscan_labels(sample, 10, cluster_selection_epsilon=0.01).  One download of the
     12 (n - 1) bytes of the tree and one upload of the labels; the rest of the device work is asynchronous apart from one 4-byte read
     per Boruvka round."""
-    from . import _lib
     _check_params("hdbscan_labels", min_cluster_size, cluster_selection_epsilon)
     if core_k is None:
         core_k = min_cluster_size if min_samples is None else min_samples

@@ -21,10 +21,11 @@ from dataclasses import dataclass
 
 import torch
 
+from . import _lib
 from ._ffi import check, ptr, stream_ptr
 
-MAX_MASKS = 1024     # MI_CONTRASTIVE_LOSS_MAX_MASKS
-MAX_SCALES = 32      # MI_CONTRASTIVE_LOSS_MAX_SCALES
+MAX_MASKS = _lib.MI_CONTRASTIVE_LOSS_MAX_MASKS
+MAX_SCALES = _lib.MI_CONTRASTIVE_LOSS_MAX_SCALES
 MAX_CHANNELS = 256
 _ROW_STATS = 8       # CL_ROW_STATS (csrc/contrastive_loss.h)
 _ACC_HEAD = 5        # class counts (3), max a, ~min a; then the M mask areas
@@ -45,7 +46,6 @@ def pack_sam_masks(masks: torch.Tensor, device=None) -> PackedSamMasks:
     """bool (M, H, W) masks (cam.original_masks), on the CPU or the device -> PackedSamMasks on `device` (default: the masks'
     device, or the current CUDA device for CPU masks).  One launch; a caller may keep the result per camera, which removes the
     per-iteration host-to-device copy of the masks."""
-    from . import _lib
     if not isinstance(masks, torch.Tensor) or masks.dtype != torch.bool or masks.dim() != 3:
         raise ValueError(f"pack_sam_masks: need a bool (M, H, W) tensor, got "
                          f"{getattr(masks, 'dtype', type(masks))} {tuple(getattr(masks, 'shape', ()))}")
@@ -137,7 +137,6 @@ def sample_contrastive_targets(masks, mask_scales: torch.Tensor, upper_bound_sca
     """train_contrastive_feature.py:145-226 without :228 (q_trans is the caller's): the sampled rays, the sampled scales and the
     per-ray, per-scale gt bitsets.  `masks` is a PackedSamMasks or bool (M, H, W) masks (packed here, on the device);
     `mask_scales` (M,) float32 in the masks' order.  Draws the reference's CPU random numbers in its order."""
-    from . import _lib
     if isinstance(masks, PackedSamMasks):
         packed = masks
     elif isinstance(masks, torch.Tensor):
@@ -195,7 +194,6 @@ class ContrastiveStats:
 class _PairLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, tg, rand, out_f32, out_i64):
-        from . import _lib
         L = _lib.load()
         N, S, C = feats.shape
         dev = feats.device
@@ -209,7 +207,6 @@ class _PairLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         L = _lib.load()
         feats, rand, out_i64 = ctx.saved_tensors
         tg = ctx.tg

@@ -67,6 +67,7 @@ int mi_train_adam_step(int n_tensors, float* const* params, const float* const* 
                        const size_t* counts, const double* step_sizes, double inv_sqrt_bc2, double beta1, double beta2, double eps, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
+    static_assert(ADAM_MAX_TENSORS == MI_TRAIN_ADAM_MAX_TENSORS, "tensors per call");
     if (n_tensors < 1 || n_tensors > ADAM_MAX_TENSORS) return fail(MI_RAST_ERR_INVALID, "adam: need 1 <= n_tensors <= 16 per call");
     if (!params || !grads || !exp_avg || !exp_avg_sq || !counts || !step_sizes) return fail(MI_RAST_ERR_INVALID, "adam: null table");
     if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) return fail(MI_RAST_ERR_INVALID, "adam: need 0 <= beta < 1");
@@ -193,6 +194,7 @@ int mi_train_densify_apply(int P, const int* counts, int n_tensors, const float*
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = densify_check_ws(P, workspace, workspace_bytes)) return rc;
     if (!counts || !src || !dst || !cols || !kinds) return fail(MI_RAST_ERR_INVALID, "densify: null table");
+    static_assert(DN_MAX_TENSORS == MI_TRAIN_DENSIFY_MAX_TENSORS, "tensors per call");
     if (n_tensors < 3 || n_tensors > DN_MAX_TENSORS) return fail(MI_RAST_ERR_INVALID, "densify: need 3 <= n_tensors <= 32");
     const long long n_split = counts[DC_SPLITS], n_orig = counts[DC_KEEP_ORIG], n_clone = counts[DC_KEEP_CLONE], n_child = counts[DC_KEEP_CHILD];
     if (counts[DC_CLONES] < 0 || n_split < 0 || n_orig < 0 || n_clone < 0 || n_child < 0 || counts[DC_CLONES] + n_split > P || n_orig + n_split > P ||

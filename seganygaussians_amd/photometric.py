@@ -18,12 +18,13 @@ from __future__ import annotations
 import torch
 from torch.autograd.function import once_differentiable
 
+from . import _lib
 from ._args import f32, number
 from ._ffi import check, stream_ptr
 
-WINDOW_SIZE = 11
-TILE_H, TILE_W = 32, 64       # MI_PHOTO_TILE_H, MI_PHOTO_TILE_W (include/mi_photometric.h)
-_L1, _SSIM = 1, 2             # MI_PHOTO_L1, MI_PHOTO_SSIM
+WINDOW_SIZE = _lib.MI_PHOTO_WINDOW
+TILE_H, TILE_W = _lib.MI_PHOTO_TILE_H, _lib.MI_PHOTO_TILE_W
+_L1, _SSIM = _lib.MI_PHOTO_L1, _lib.MI_PHOTO_SSIM
 
 
 def _prepare(who: str, image, gt, names=("image", "gt")):
@@ -52,7 +53,6 @@ def _prepare(who: str, image, gt, names=("image", "gt")):
 
 def _forward(image, gt, dims, lambda_dssim: float, parts: int, want_maps: bool):
     """Launches the forward.  Returns (out, maps): out float32 (3 + 2 B,) = loss, l1, ssim, then per image l1, ssim."""
-    from . import _lib
     L = _lib.load()
     B, C, H, W = dims
     dev = image.device
@@ -66,7 +66,6 @@ def _forward(image, gt, dims, lambda_dssim: float, parts: int, want_maps: bool):
 
 
 def _backward(image, gt, maps, dims, grad_out, per_image: bool, w_l1: float, w_ssim: float):
-    from . import _lib
     L = _lib.load()
     B, C, H, W = dims
     dev = image.device

@@ -22,13 +22,14 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
 from ._args import f32, no_grad_one_gpu, number
 from ._ffi import check, ptr, stream_ptr
 
-MAX_CHANNELS = 256
-MAX_QUERIES = 16
-MAX_CENTERS = 4096
-PRE_MODES = {"none": 0, "l2": 1, "eps": 2}
+MAX_CHANNELS = _lib.MI_SEGMENT_MAX_CHANNELS
+MAX_QUERIES = _lib.MI_SEGMENT_MAX_QUERIES
+MAX_CENTERS = _lib.MI_SEGMENT_MAX_CENTERS
+PRE_MODES = _lib.MI_SEGMENT_PRE
 
 
 def feature_table(who: str, features):
@@ -99,7 +100,6 @@ def similarity_scores(features: torch.Tensor, queries: torch.Tensor, gates: torc
     to the same chain and composes the display buffer in the one read of the image.
     features: float32 (C, H, W) or (P, C); a non-contiguous tensor is copied.  queries: float32 (Q, C) or (C,), used as given.
     gates: float32, C values, or None."""
-    from . import _lib
     features, queries, gates, layout, N, C, Q, shape = _prepare("similarity_scores", features, queries, gates, pre, MAX_QUERIES, "queries")
     L = _lib.load()
     dev = features.device
@@ -116,7 +116,6 @@ def select_by_similarity(features: torch.Tensor, queries: torch.Tensor, threshol
 
     t_k = (s_k + 1) / 2 with half_shift (the GUI), t_k = s_k without (the notebook's `similarities > 0.75`).  Returns
     (mask, score): mask bool = any_k t_k > threshold, score float32 = max_k (t_k > threshold ? t_k : 0), shaped (H, W) or (P,)."""
-    from . import _lib
     features, queries, gates, layout, N, C, Q, shape = _prepare("select_by_similarity", features, queries, gates, pre, MAX_QUERIES, "queries")
     threshold = number("select_by_similarity", "threshold", threshold)
     L = _lib.load()
@@ -134,7 +133,6 @@ def assign_clusters(features: torch.Tensor, centers: torch.Tensor, gates: torch.
 
     Returns (labels, best): labels int32 = argmax_k s_k (the lowest index among equal maxima, as torch.argmax on the CPU), best
     float32 = max_k s_k, shaped (H, W) or (P,).  centers: float32 (K, C), used as given."""
-    from . import _lib
     features, centers, gates, layout, N, C, K, shape = _prepare("assign_clusters", features, centers, gates, pre, MAX_CENTERS, "centers")
     L = _lib.load()
     dev = features.device

@@ -18,11 +18,12 @@ import math
 import torch
 from torch.optim.optimizer import _get_scalar_dtype     # the dtype torch.optim.Adam gives its 'step'
 
+from . import _lib
 from ._ffi import check, stream_ptr
 
-GROUP_KINDS = {"xyz": 2, "scaling": 3, "rotation": 4}     # MI_TRAIN_XYZ, MI_TRAIN_SCALING, MI_TRAIN_ROTATION; every other name: a copy
-_COPY, _MOMENT = 0, 1
-ADAM_MAX_TENSORS = 16
+GROUP_KINDS = {"xyz": _lib.MI_TRAIN_XYZ, "scaling": _lib.MI_TRAIN_SCALING, "rotation": _lib.MI_TRAIN_ROTATION}     # every other name: a copy
+_COPY, _MOMENT = _lib.MI_TRAIN_COPY, _lib.MI_TRAIN_MOMENT
+ADAM_MAX_TENSORS = _lib.MI_TRAIN_ADAM_MAX_TENSORS
 
 
 def _dense_f32(t) -> bool:
@@ -90,7 +91,6 @@ class FusedAdam(torch.optim.Adam):
                 t = float(state["step"])
                 key = (p.device, 1.0 / math.sqrt(1.0 - beta2 ** t), beta1, beta2, eps)
                 launches.setdefault(key, []).append((p, p.grad, state["exp_avg"], state["exp_avg_sq"], lr / (1.0 - beta1 ** t)))
-        from . import _lib
         L = _lib.load()
         for (dev, inv_sqrt_bc2, beta1, beta2, eps), rows in launches.items():
             with torch.cuda.device(dev):
@@ -128,7 +128,6 @@ def densification_stats(accum, denom, viewspace_grad, radii, max_radii2D=None) -
             raise ValueError(f"densification_stats: {name} must be on the GPU of viewspace_grad, got {t.device} (there is no CPU fallback)")
     if P == 0:
         return
-    from . import _lib
     L = _lib.load()
     grad = viewspace_grad.contiguous()
     radii = radii.to(torch.int32).contiguous()
@@ -175,7 +174,6 @@ def densify_and_prune(params: dict, optimizer, accum, denom, max_radii2D, max_gr
 
     if P == 0:
         return dict(params), *zeros_stats(0)
-    from . import _lib
     L = _lib.load()
     src, kinds, names = [], [], []      # names: (group name, state key or None)
     for name, t in params.items():

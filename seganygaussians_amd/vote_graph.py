@@ -15,16 +15,17 @@ from __future__ import annotations
 
 import torch
 
+from . import _lib
 from ._args import f32, no_grad_one_gpu, number, size_hw
 from ._ffi import check, stream_ptr
-from .clustering import MAX_POINTS, MAX_WORDS
+from .clustering import MAX_POINTS
 from .contrastive_loss import MAX_MASKS, PackedSamMasks
 from .mask_scales import as_packed, erode
 
 MAX_CHANNELS = 256
-MAX_ANCHORS = 32 * MAX_WORDS
-MAX_EMBED_DIM = 1024
-MAX_PROMPTS = 16
+MAX_ANCHORS = _lib.MI_VOTE_MAX_ANCHORS     # 32 MI_CLUSTER_MAX_WORDS
+MAX_EMBED_DIM = _lib.MI_VOTE_MAX_EMBED_DIM
+MAX_PROMPTS = _lib.MI_VOTE_MAX_PROMPTS
 
 
 def _f32_matrix(who: str, name: str, t, rows=None, cols=None) -> None:
@@ -46,7 +47,6 @@ def sam_mask_features(rendered: torch.Tensor, masks, gates: torch.Tensor, size=N
 
     Returns float32 (M, C); an empty mask gives a zero row.  With return_counts, also n_m as int64 (M,).  The same inputs give the
     same bits on any stream."""
-    from . import _lib
     who = "sam_mask_features"
     f32(who, "rendered", rendered)
     if rendered.dim() != 3:
@@ -96,7 +96,6 @@ def anchor_bits(mask_features: torch.Tensor, gates: torch.Tensor, anchor_feature
     hdbscan_labels(metric="jaccard").  out: a contiguous int32 (M_total, ceil(A / 32)) tensor to fill instead, rows
     row_offset .. row_offset + M - 1 (the view of those rows is returned), so that a scene is filled view by view.
     With return_counts, also the set bits per row as int32 (M,)."""
-    from . import _lib
     who = "anchor_bits"
     _f32_matrix(who, "mask_features", mask_features)
     M, C = int(mask_features.shape[0]), int(mask_features.shape[1])
@@ -145,7 +144,6 @@ def clip_relevancy(embeds: torch.Tensor, pos_embeds: torch.Tensor, neg_embeds: t
 
     embeds: float32 or float16 (N, D), 1 <= D <= 1024; with normalize, e_n = row.float() / max(|row|, 1e-12).  pos_embeds float32
     (P, D), neg_embeds float32 (Q, D), used as given, 1 <= P, Q <= 16.  Returns float32 (N, P)."""
-    from . import _lib
     who = "clip_relevancy"
     if not isinstance(embeds, torch.Tensor) or embeds.dtype not in (torch.float32, torch.float16):
         raise ValueError(f"{who}: embeds must be a float32 or float16 tensor, got {getattr(embeds, 'dtype', type(embeds))}")

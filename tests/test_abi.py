@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI boundary: the HIP library builds for gfx950, loads, and exports every
-symbol the headers in include/ declare; host-side helpers agree with the oracle.  No compute calls (no GPU)."""
+symbol the headers in include/ declare; what _lib.py reads off the headers (signatures, constants) is what a C++ compiler reads;
+host-side helpers agree with the oracle.  No compute calls (no GPU)."""
 import ctypes
 import os
 import re
@@ -20,14 +21,94 @@ def lib():
 
 def test_header_symbols_exported(lib):
     """Every function that a header in include/ declares is listed in _lib.ALL_EXPORTS and resolves in the library, and nothing else
-    is listed."""
+    is listed; each is declared in exactly one header, the one _lib.DECLARED lists it under."""
     hdr = "".join(open(h).read() for h in build.HEADERS)
     declared = set(re.findall(r"\b(mi_[a-z_0-9]+)\s*\(", hdr)) - {"mi_rast_resize_fn"}
     assert len(build.HEADERS) == 7 and len(_lib.ALL_EXPORTS) == len(set(_lib.ALL_EXPORTS))
     assert declared == set(_lib.ALL_EXPORTS), declared ^ set(_lib.ALL_EXPORTS)
+    code = {os.path.basename(h): re.sub(r"/\*.*?\*/", " ", open(h).read(), flags=re.S) for h in build.HEADERS}   # comments name functions too
     for name in declared:
         assert hasattr(lib, name), name
         assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
+        where = [h for h, text in code.items() for _ in re.findall(rf"\b{name}\s*\(", text)]
+        assert len(where) == 1 and name in _lib.DECLARED[where[0]], (name, where)
+
+
+# ---- the compiler as witness: what a C++ compiler makes of the headers is what _lib read off them ----
+_WITNESS = r"""
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <type_traits>
+%(includes)s
+template <class T, bool is_return> constexpr char code() {
+    if constexpr (std::is_void_v<T>) return 'v';
+    else if constexpr (is_return && std::is_same_v<T, const char*>) return 's';
+    else if constexpr (std::is_same_v<T, mi_rast_resize_fn>) return 'c';
+    else if constexpr (std::is_pointer_v<T>) return 'p';
+    else if constexpr (std::is_same_v<T, int>) return 'i';
+    else if constexpr (std::is_same_v<T, uint32_t>) return 'u';
+    else if constexpr (std::is_same_v<T, size_t>) return 'z';
+    else if constexpr (std::is_same_v<T, float>) return 'f';
+    else if constexpr (std::is_same_v<T, double>) return 'd';
+    else return '?';
+}
+template <class F> struct Sig;
+template <class R, class... A> struct Sig<R (*)(A...)> {
+    static void print(const char* name) { const char p[] = {code<A, false>()..., 0}; std::printf("F %%s %%c %%s\n", name, code<R, true>(), p); }
+};
+int main() {
+%(body)s
+}
+"""
+_CODES = {None: "v", ctypes.c_char_p: "s", _lib.RESIZE_FN: "c", ctypes.c_void_p: "p", ctypes.c_int: "i", ctypes.c_uint32: "u",
+          ctypes.c_size_t: "z", ctypes.c_float: "f", ctypes.c_double: "d"}
+
+
+def test_compiler_reads_the_headers_as_lib_does(tmp_path):
+    """A host-only C++ program prints the class of the return type and of every parameter of each declared function, taken from
+    decltype(&name) (nothing is linked against the library), and the value of every constant; both must be _lib's tables."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or next(p for p in ("/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++") if os.path.exists(p))
+    body = [f'    Sig<decltype(&{n})>::print("{n}");' for n in _lib.ALL_EXPORTS]
+    body += [f'    std::printf("C {n} %lld\\n", (long long)({n}));' for n in _lib.CONSTANTS]
+    (src := tmp_path / "witness.cpp").write_text(_WITNESS % {"includes": "\n".join(f'#include "{os.path.basename(h)}"' for h in build.HEADERS), "body": "\n".join(body)})
+    subprocess.check_call([cxx, "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "witness")])
+    lines = [line.split(" ") for line in subprocess.check_output([str(tmp_path / "witness")], text=True).splitlines()]
+    seen = {l[1]: (l[2], l[3]) for l in lines if l[0] == "F"}     # "F name v " for an empty parameter list: l[3] == ""
+    assert len(seen) == len(_lib.SIGNATURES) == 73 and len(lines) == 73 + len(_lib.CONSTANTS)
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        assert seen[name] == (_CODES[restype], "".join(_CODES[a] for a in argtypes)) and "?" not in "".join(seen[name]), name
+    assert {l[1]: int(l[2]) for l in lines if l[0] == "C"} == _lib.CONSTANTS
+
+
+@pytest.mark.parametrize("text, named", [
+    ("int mi_f(int n, long double x);", "mi_f"), ("int mi_f(float v[3]);", "mi_f"), ("int mi_f(int n, mi_handle_t h);", "mi_f"),
+    ("int mi_f(char* (*resize)(size_t nbytes, void* user), void* user);", "mi_f"), ("#define MI_X 1.5", "MI_X")])
+def test_parser_refuses_what_it_does_not_understand(text, named):
+    with pytest.raises(_lib.MiRastError, match=rf"mi_some\.h: .*\b{named}\b"):
+        _lib.parse_header("int mi_ok(void);\n" + text + "\n", "mi_some.h")
+
+
+def test_parser_skips_comments_and_guards_and_counts_enumerators():
+    assert _lib.parse_header("/* int mi_f(int x); */\n// int mi_g(void);\n") == ([], {})
+    functions, constants = _lib.parse_header(
+        "#ifndef MI_T_H\n#define MI_T_H\n#define MI_E (1 << 4)   /* int mi_h(void); */\nenum { MI_A = 3, MI_B, MI_C = 0x10, MI_D };\n"
+        "const char* mi_s(void);\nvoid mi_v(const float* const* t, uint32_t m, mi_rast_resize_fn f);\n#endif\n")
+    assert constants == {"MI_E": 16, "MI_A": 3, "MI_B": 4, "MI_C": 16, "MI_D": 17}
+    assert functions == [("mi_s", ctypes.c_char_p, []), ("mi_v", None, [ctypes.c_void_p, ctypes.c_uint32, _lib.RESIZE_FN])]
+
+
+def test_lib_binds_in_one_loop_only():
+    """_lib.py states no signature of its own: restype and argtypes are assigned once, in the loop over SIGNATURES, no header text is
+    evaluated, and the hand-kept export lists are gone."""
+    src = open(_lib.__file__).read().splitlines()
+    hits = [k for k, line in enumerate(src) if re.search(r"\.(argtypes|restype)\b", line)]
+    assert len(hits) == 1 and src[hits[0]].strip() == "fn.restype, fn.argtypes = restype, argtypes"
+    assert src[hits[0] - 2].strip() == "for name, (restype, argtypes) in SIGNATURES.items():"
+    assert not re.search(r"\b(eval|exec)\s*\(", "\n".join(src))
+    assert [n for n in vars(_lib) if n.endswith("EXPORTS")] == ["ALL_EXPORTS"]
 
 
 # one call per host file of csrc/ that is refused for its arguments before any HIP call (the pointers are never read), and its message

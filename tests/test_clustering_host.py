@@ -302,7 +302,8 @@ def lib():
 def test_abi_exported_and_checks_arguments(lib):
     hdr = open(os.path.join(ROOT, "include", "mi_segment.h")).read()
     declared = set(re.findall(r"\b(mi_cluster_[a-z_0-9]+)\s*\(", hdr))
-    assert declared == set(_lib.CLUSTER_EXPORTS) and set(_lib.CLUSTER_EXPORTS) <= set(_lib.ALL_EXPORTS)
+    assert declared == {"mi_cluster_workspace_bytes", "mi_cluster_core_distances", "mi_cluster_mst", "mi_cluster_mst_rounds",
+                        "mi_cluster_labels_host"} <= set(_lib.ALL_EXPORTS)
     for name in declared:
         assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
     assert {"cluster.h", "cluster_tree.h", "mi_cluster.hip"} <= set(build.SOURCES)
@@ -312,7 +313,8 @@ def test_abi_exported_and_checks_arguments(lib):
                         ("MI_CLUSTER_MAX_CHANNELS", 256), ("MI_CLUSTER_MAX_WORDS", 1024), ("MI_CLUSTER_MAX_CORE_K", 64)):
         assert f"#define {name} {value}\n" in hdr
     assert (cl.MAX_POINTS, cl.MAX_CHANNELS, cl.MAX_WORDS, cl.MAX_CORE_K) == (1 << 20, 256, 1024, 64)
-    assert cl.METRICS == _lib.MI_CLUSTER_METRIC
+    assert (1 << 20, 256, 1024, 64) == tuple(getattr(_lib, "MI_CLUSTER_MAX_" + n) for n in ("POINTS", "CHANNELS", "WORDS", "CORE_K"))
+    assert cl.METRICS == _lib.MI_CLUSTER_METRIC == {"euclidean": _lib.MI_CLUSTER_EUCLIDEAN, "jaccard": _lib.MI_CLUSTER_JACCARD}
     # refused for their arguments before any HIP call: the pointers are never read
     ws = lib.mi_cluster_workspace_bytes(0, 100, 32, 10)
     assert lib.mi_cluster_core_distances(2, 100, 32, 8, 10, 8, 8, ws, None) != 0 and "metric" in _lib.last_error()

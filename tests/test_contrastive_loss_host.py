@@ -6,7 +6,7 @@ import ctypes
 import pytest
 import torch
 
-from seganygaussians_amd import _lib, build
+from seganygaussians_amd import _lib, build, contrastive_loss as cl
 from seganygaussians_amd.contrastive_loss import (PackedSamMasks, contrastive_loss, draw_sampled_scales, pack_sam_masks,
                                                   sample_contrastive_targets)
 
@@ -119,9 +119,12 @@ def test_bad_inputs_refused_before_any_launch():
 def test_loss_abi_exported():
     build.build_library()
     L = _lib.load()
-    for name in ("mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
-                 "mi_contrastive_loss_backward"):
-        assert name in _lib.EXPORTS
+    names = ["mi_contrastive_pack_masks", "mi_contrastive_cover", "mi_contrastive_targets", "mi_contrastive_loss_forward",
+             "mi_contrastive_loss_backward"]
+    assert _lib.DECLARED["mi_contrastive.h"][2:] == names            # the header's second section: the loss itself
+    assert (cl.MAX_MASKS, cl.MAX_SCALES) == (1024, 32) == (_lib.MI_CONTRASTIVE_LOSS_MAX_MASKS, _lib.MI_CONTRASTIVE_LOSS_MAX_SCALES)
+    for name in names:
+        assert name in _lib.ALL_EXPORTS
         assert ctypes.cast(getattr(L, name), ctypes.c_void_p).value
     # argument checks run before any launch: no device needed
     assert L.mi_contrastive_pack_masks(1025, 4, 4, None, None, None) != 0

@@ -136,8 +136,7 @@ def test_abi_exported_and_checks_arguments():
     L = _lib.load()
     hdr = open(os.path.join(ROOT, "include", "mi_photometric.h")).read()
     declared = set(re.findall(r"\b(mi_photo_[a-z_0-9]+)\s*\(", hdr.split("#ifndef")[1]))
-    assert declared == set(_lib.PHOTOMETRIC_EXPORTS)
-    assert not set(_lib.PHOTOMETRIC_EXPORTS) & set(_lib.EXPORTS + _lib.MASK_SCALES_EXPORTS + _lib.SEGMENT_EXPORTS)
+    assert declared == {"mi_photo_loss_workspace_bytes", "mi_photo_loss_window", "mi_photo_loss_forward", "mi_photo_loss_backward"} <= set(_lib.ALL_EXPORTS)
     for name in declared:
         assert ctypes.cast(getattr(L, name), ctypes.c_void_p).value
     assert os.path.join(ROOT, "include", "mi_photometric.h") in build.HEADERS and "photometric.h" in build.SOURCES
@@ -147,7 +146,7 @@ def test_abi_exported_and_checks_arguments():
     assert ws(1, ph.TILE_H + 1, ph.TILE_W) == 32 and ws(1, ph.TILE_H, ph.TILE_W + 1) == 32
     assert ws(3, 1080, 1920) == 3 * 34 * 30 * 16
     assert ws(0, 4, 4) == 0 and ws(1, 0, 4) == 0 and ws(2, 1 << 15, 1 << 15) == 0
-    assert (_lib.MI_PHOTO_L1, _lib.MI_PHOTO_SSIM) == (ph._L1, ph._SSIM) == (1, 2)
+    assert (_lib.MI_PHOTO_L1, _lib.MI_PHOTO_SSIM, _lib.MI_PHOTO_WINDOW) == (ph._L1, ph._SSIM, ph.WINDOW_SIZE) == (1, 2, 11)
     # argument checks run before any launch: no device needed
     fwd, bwd = L.mi_photo_loss_forward, L.mi_photo_loss_backward
     assert fwd(0, 3, 4, 4, 8, 8, 0.2, 3, None, 8, 1 << 20, 8, None) != 0 and ">= 1" in _lib.last_error()

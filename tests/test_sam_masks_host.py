@@ -67,8 +67,9 @@ def test_restatement_fallbacks_and_quirks():
 def test_exports_resolve():
     build.build_library()
     L = _lib.load()
-    assert _lib.MASK_SETS_EXPORTS == ["mi_mask_overlaps", "mi_mask_boxes", "mi_mask_nms_keep", "mi_mask_score_images"]
-    for name in _lib.MASK_SETS_EXPORTS:
+    names = ["mi_mask_overlaps", "mi_mask_boxes", "mi_mask_nms_keep", "mi_mask_score_images"]
+    assert _lib.DECLARED["mi_mask_scales.h"][4:8] == names           # the header's second section
+    for name in names:
         assert name in _lib.ALL_EXPORTS
         assert ctypes.cast(getattr(L, name), ctypes.c_void_p).value
     for name in ("mask_overlaps", "masks_to_boxes", "mask_nms", "masks_update", "mask_score_images"):

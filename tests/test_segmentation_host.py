@@ -161,8 +161,9 @@ def test_abi_exported_and_checks_arguments():
     L = _lib.load()
     hdr = open(os.path.join(ROOT, "include", "mi_segment.h")).read()
     declared = set(re.findall(r"\b(mi_segment_[a-z_0-9]+)\s*\(", hdr))
-    assert declared == set(_lib.SEGMENT_EXPORTS)
-    assert not set(_lib.SEGMENT_EXPORTS) & set(_lib.EXPORTS)
+    assert declared == {"mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"} <= set(_lib.ALL_EXPORTS)
+    assert (seg.MAX_CHANNELS, seg.MAX_QUERIES, seg.MAX_CENTERS) == (_lib.MI_SEGMENT_MAX_CHANNELS, _lib.MI_SEGMENT_MAX_QUERIES, _lib.MI_SEGMENT_MAX_CENTERS)
+    assert seg.PRE_MODES == _lib.MI_SEGMENT_PRE == {"none": _lib.MI_SEGMENT_PRE_NONE, "l2": _lib.MI_SEGMENT_PRE_L2, "eps": _lib.MI_SEGMENT_PRE_EPS}
     for name in declared:
         assert ctypes.cast(getattr(L, name), ctypes.c_void_p).value
     assert os.path.join(ROOT, "include", "mi_segment.h") in build.HEADERS and "segment.h" in build.SOURCES
@@ -189,4 +190,4 @@ def test_abi_exported_and_checks_arguments():
 def test_module_exports():
     assert callable(seg.similarity_scores) and callable(seg.select_by_similarity) and callable(seg.assign_clusters)
     assert seg.MAX_CHANNELS == 256 and seg.MAX_QUERIES == 16 and seg.MAX_CENTERS == 4096
-    assert seg.PRE_MODES == _lib.MI_SEGMENT_PRE
+    assert seg.PRE_MODES == _lib.MI_SEGMENT_PRE == {"none": 0, "l2": 1, "eps": 2}

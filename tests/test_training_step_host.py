@@ -29,16 +29,17 @@ def lib():
 def test_exports_are_a_section_of_mi_rast_h(lib):
     hdr = open(os.path.join(ROOT, "include", "mi_rast.h")).read()
     declared = set(re.findall(r"\b(mi_train_[a-z_0-9]+)\s*\(", hdr))
-    assert declared == set(_lib.TRAIN_STEP_EXPORTS) and 4 <= len(declared) <= 6
+    assert declared == {"mi_train_adam_step", "mi_train_densify_stats", "mi_train_densify_workspace_bytes", "mi_train_densify_plan",
+                        "mi_train_densify_counts", "mi_train_densify_apply"} <= set(_lib.ALL_EXPORTS)
     assert hdr.index("mi_train_adam_step") > hdr.index("mi_rast_profile_read")           # a section of its own at the end
-    others = _lib.EXPORTS + _lib.MASK_SCALES_EXPORTS + _lib.SEGMENT_EXPORTS + _lib.PHOTOMETRIC_EXPORTS
-    assert not set(_lib.TRAIN_STEP_EXPORTS) & set(others) and _lib.ALL_EXPORTS == others + _lib.TRAIN_STEP_EXPORTS
     for name in declared:
         assert C.cast(getattr(lib, name), C.c_void_p).value
     assert "train_step.h" in build.SOURCES and "mi_train_step.hip" in build.SOURCES
     includers = [f for f in build.SOURCES if '"train_step.h"' in open(os.path.join(build.SRC_DIR, f)).read()]
     assert includers == ["mi_train_step.hip"]
     assert (_lib.MI_TRAIN_XYZ, _lib.MI_TRAIN_SCALING, _lib.MI_TRAIN_ROTATION) == tuple(ts.GROUP_KINDS[k] for k in ("xyz", "scaling", "rotation"))
+    assert ts.GROUP_KINDS == {"xyz": 2, "scaling": 3, "rotation": 4} and ts.ADAM_MAX_TENSORS == _lib.MI_TRAIN_ADAM_MAX_TENSORS == 16
+    assert "#define MI_TRAIN_ADAM_MAX_TENSORS 16\n" in hdr and "#define MI_TRAIN_DENSIFY_MAX_TENSORS 32\n" in hdr
     for k, name in enumerate(("MI_TRAIN_COPY", "MI_TRAIN_MOMENT", "MI_TRAIN_XYZ", "MI_TRAIN_SCALING", "MI_TRAIN_ROTATION")):
         assert re.search(rf"{name} = {k}\b", hdr)
 

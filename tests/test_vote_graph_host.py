@@ -131,8 +131,11 @@ def test_clip_relevancy_refusals(args, msg):
 def test_c_abi_refuses_before_any_launch():
     build.build_library()
     L = _lib.load()
-    for name in _lib.VOTE_GRAPH_EXPORTS + ["mi_mask_erode_min_sum"]:
-        assert hasattr(L, name), name
+    names = ["mi_vote_mask_features_workspace_bytes", "mi_vote_mask_features", "mi_vote_anchor_bits", "mi_vote_relevancy"]
+    assert [n for n in _lib.DECLARED["mi_segment.h"] if n.startswith("mi_vote_")] == names
+    for name in names + ["mi_mask_erode_min_sum"]:
+        assert name in _lib.ALL_EXPORTS and hasattr(L, name), name
+    assert (vg.MAX_ANCHORS, vg.MAX_EMBED_DIM, vg.MAX_PROMPTS) == (32768, 1024, 16) == tuple(_lib.CONSTANTS["MI_VOTE_MAX_" + n] for n in ("ANCHORS", "EMBED_DIM", "PROMPTS"))
     assert L.mi_vote_mask_features_workspace_bytes(0, 4, 8, 8) == 0 and L.mi_vote_mask_features_workspace_bytes(2, 257, 8, 8) == 0
     T = 2 * 2   # ceil(17 / 16) * ceil(65 / 64) tiles
     assert L.mi_vote_mask_features_workspace_bytes(3, 4, 17, 65) >= 4 * 4 * 17 * 65 + 8 * 3 * T * (4 + 1)
