@@ -22,7 +22,7 @@ import torch
 from . import _lib
 from ._args import check_out, number, size_hw
 from ._ffi import check, stream_ptr
-from .mask_scales import as_packed, check_shape
+from .packed_masks import as_packed, check_shape
 from .sam_masks import resize_sam_masks
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)   # clip_utils/clip_utils.py:64

@@ -23,44 +23,12 @@ import torch
 
 from . import _lib
 from ._ffi import check, ptr, stream_ptr
+from .packed_masks import MAX_MASKS, PackedSamMasks, pack_sam_masks   # their home; all three stay names of this module
 
-MAX_MASKS = _lib.MI_CONTRASTIVE_LOSS_MAX_MASKS
 MAX_SCALES = _lib.MI_CONTRASTIVE_LOSS_MAX_SCALES
 MAX_CHANNELS = 256
 _ROW_STATS = 8       # CL_ROW_STATS (csrc/contrastive_loss.h)
 _ACC_HEAD = 5        # class counts (3), max a, ~min a; then the M mask areas
-
-
-@dataclass
-class PackedSamMasks:
-    """Bit-packed SAM masks on the device: words (M, H, ceil(W / 64)) int64, bit b of word q = pixel 64 q + b."""
-    words: torch.Tensor
-    shape: tuple   # (M, H, W)
-
-    @property
-    def device(self):
-        return self.words.device
-
-
-def pack_sam_masks(masks: torch.Tensor, device=None) -> PackedSamMasks:
-    """bool (M, H, W) masks (cam.original_masks), on the CPU or the device -> PackedSamMasks on `device` (default: the masks'
-    device, or the current CUDA device for CPU masks).  One launch; a caller may keep the result per camera, which removes the
-    per-iteration host-to-device copy of the masks."""
-    if not isinstance(masks, torch.Tensor) or masks.dtype != torch.bool or masks.dim() != 3:
-        raise ValueError(f"pack_sam_masks: need a bool (M, H, W) tensor, got "
-                         f"{getattr(masks, 'dtype', type(masks))} {tuple(getattr(masks, 'shape', ()))}")
-    M, H, W = (int(v) for v in masks.shape)
-    if not 1 <= M <= MAX_MASKS or H < 1 or W < 1:
-        raise ValueError(f"pack_sam_masks: need 1 <= M <= {MAX_MASKS} masks and a non-empty image, got {(M, H, W)}")
-    dev = torch.device(device) if device is not None else (masks.device if masks.is_cuda else torch.device("cuda", torch.cuda.current_device()))
-    if dev.type != "cuda":
-        raise ValueError(f"pack_sam_masks: the packed masks live on a GPU, not on {dev}")
-    L = _lib.load()
-    src = masks.to(dev).contiguous()
-    words = torch.empty((M, H, (W + 63) // 64), device=dev, dtype=torch.int64)
-    with torch.cuda.device(dev):
-        check(L.mi_contrastive_pack_masks(M, H, W, src.data_ptr(), words.data_ptr(), stream_ptr(dev)))
-    return PackedSamMasks(words, (M, H, W))
 
 
 def draw_sampled_scales(sorted_scales: torch.Tensor, sampled_scale_index: torch.Tensor, upper_bound_scale: float,

@@ -11,13 +11,14 @@
 //               weights.  The source rows come in ASCENDING order, so every output element is the width-pass values times their
 //               height weights summed in ascending source row: the order the tests' bound assumes.  Both tap loops run over the taps
 //               the crop gives; nothing bounds them but the crop.  Stores are coalesced along Sw.
-//               antialias off: two taps per axis, a l0 + b l1 along the width and fmaf(t0, wy0, t1 wy1) along the height, the order of
+//               antialias off: pm_source_taps per axis, a l0 + b l1 along the width and fmaf(t0, wy0, t1 wy1) along the height, the order of
 //               PyTorch's CPU upsample_bilinear2d that ms_resize_kernel (mask_scales.h) has too.
 //   index map : one wave per word of the image, one lane per pixel.  The lanes fetch the word of 64 masks at once; the masks that
 //               have a bit in the word are walked in ascending order and the last that covers a pixel stays.
 #pragma once
 
 #include "../../include/mi_mask_scales.h"
+#include "packed_masks.h"
 
 #include <hip/hip_fp16.h>
 
@@ -68,20 +69,6 @@ __device__ inline float ct_aa_total(const CtAxis& a, float center, int lo, int h
     return total;
 }
 
-// the two taps of upsample_bilinear2d (align_corners=False): ms_source_taps of mask_scales.h, restated here because that header
-// keeps its single includer
-__device__ inline void ct_source_taps(float scale, int dst, int in_size, int& i0, int& i1, float& l0, float& l1)
-{
-    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-    src = src < 0.f ? 0.f : src;
-    const int idx = min((int)floorf(src), in_size - 1);
-    const float lam = fminf(fmaxf(src - (float)idx, 0.f), 1.f);
-    i0 = idx;
-    i1 = idx + (idx < in_size - 1 ? 1 : 0);
-    l1 = lam;
-    l0 = 1.f - lam;
-}
-
 __device__ inline void ct_store(float* p, float v) { *p = v; }
 __device__ inline void ct_store(__half* p, float v) { *p = __float2half_rn(v); }
 
@@ -129,7 +116,7 @@ __global__ void __launch_bounds__(CT_THREADS) ct_tiles_kernel(int H, int W, int 
             s_yi[0][tid] = lo;
             s_yi[1][tid] = hi;
         } else {
-            ct_source_taps(ay.scale, r, PH, s_yi[0][tid], s_yi[1][tid], s_yw[0][tid], s_yw[1][tid]);
+            pm_source_taps(ay.scale, r, PH, s_yi[0][tid], s_yi[1][tid], s_yw[0][tid], s_yw[1][tid]);
         }
     }
     __syncthreads();
@@ -146,7 +133,7 @@ __global__ void __launch_bounds__(CT_THREADS) ct_tiles_kernel(int H, int W, int 
                 ct_aa_span(ax, j, xc, xa, xb);
                 xt = ct_aa_total(ax, xc, xa, xb);
             } else {
-                ct_source_taps(ax.scale, j, PW, xa, xb, xc, xt);
+                pm_source_taps(ax.scale, j, PW, xa, xb, xc, xt);
             }
         }
         float acc[CT_BAND][3];
@@ -167,7 +154,7 @@ __global__ void __launch_bounds__(CT_THREADS) ct_tiles_kernel(int H, int W, int 
                     const int cx = c_lo + e / 3 - ox;
                     const long long X = (long long)X0 + cx;
                     float v = bg;
-                    if (row_in && cx >= 0 && cx < cw && X >= 0 && X < W && ((mrow[X >> 6] >> (X & 63)) & 1ull))
+                    if (row_in && cx >= 0 && cx < cw && X >= 0 && X < W && pm_bit(mrow, X))
                         v = s_lut[irow[3 * X + e % 3]];
                     s_row[e] = v;
                 }

@@ -27,6 +27,7 @@ constexpr int CT_MAX_CPL = 4;       // channels per lane of a ray's wave: C <= 2
 // builds contract that expression into ONE fused multiply-add, on the CPU as on the GPU; this file is compiled with
 // -ffp-contract=off, so the fmaf is spelled out: the unfused form lands one ulp of src (up to 3e-5 of a weight at 1080 rows)
 // away at a few indices of a non-trivial resize (tests/test_contrastive_frontend_edges.py pins the taps to F.interpolate).
+// Not pm_source_taps (packed_masks.h), the same source index: lam is not clamped to [0, 1] here, and the kernels' code would change.
 __device__ __forceinline__ void bilinear_tap(int dst, int n_out, int n_in, int& i0, int& i1, float& lam)
 {
     const float scale = (float)n_in / (float)n_out;

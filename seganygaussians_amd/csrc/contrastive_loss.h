@@ -17,13 +17,12 @@
 #pragma once
 
 #include "../../include/mi_contrastive.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "packed_masks.h"
 
 namespace mirast {
 
 constexpr int CL_THREADS = 256;
-constexpr int CL_MAX_WORDS = MI_CONTRASTIVE_LOSS_MAX_MASKS / 64;
+constexpr int CL_MAX_WORDS = PM_MAX_MASKS / 64;
 constexpr int CL_ROW_STATS = 8;   // per-row partials: pos sum, neg sum, pos pairs, neg pairs, cos+ sum, cos+ count, cos- sum, cos- count
 
 // ---- pack --------------------------------------------------------------------------------------------------------------------
@@ -94,7 +93,7 @@ __global__ void __launch_bounds__(CL_THREADS) cl_targets_kernel(int M, int H, in
     for (int it = 0; it < Wd; it++) {
         const int k = it * 64 + lane;
         int bit = 0;
-        if (k < M) bit = (int)((packed[((size_t)sort_idx[k] * H + y) * Wq + (x >> 6)] >> (x & 63)) & 1ull);
+        if (k < M) bit = (int)pm_bit(packed + ((size_t)sort_idx[k] * H + y) * Wq, x);
         const uint64_t b = __ballot(bit);
         if (lane == it) bits = b;
     }

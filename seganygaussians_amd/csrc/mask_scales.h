@@ -16,6 +16,7 @@
 #pragma once
 
 #include "../../include/mi_mask_scales.h"
+#include "packed_masks.h"
 #include "wave.h"
 
 namespace mirast {
@@ -23,13 +24,6 @@ namespace mirast {
 constexpr int MS_THREADS = 256;
 constexpr int MS_TILE_ROWS = 16;
 constexpr int MS_STATS = 5;   // per (mask, tile): count, sum x, sum y, sum z, sum |p|^2
-
-// the valid-pixel bits of word q of a W-pixel row
-__device__ inline uint64_t ms_valid_bits(int W, int q)
-{
-    const int n = W - 64 * q;
-    return n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-}
 
 // ---- erode, same size: bit-sliced "count of the 3x3 window >= k", 0 <= k <= 15 -------------------------------------------------
 __global__ void __launch_bounds__(MS_THREADS) ms_erode_same_kernel(int M, int H, int W, int Wq, const uint64_t* __restrict__ in, int k,
@@ -71,27 +65,11 @@ __global__ void __launch_bounds__(MS_THREADS) ms_erode_same_kernel(int M, int H,
         gt |= eq & bit[b] & ~kb;
         eq &= ~(bit[b] ^ kb);
     }
-    out[i] = (gt | eq) & ms_valid_bits(W, q);
+    out[i] = (gt | eq) & pm_valid_bits(W, q);
 }
 
 // ---- erode, resampled: PyTorch's CPU bilinear weights (UpSampleKernel.cpp, align_corners=False) --------------------------------
-// PyTorch's CPU build rounds scale * (dst + 0.5) - 0.5 and the height pass t0 w0 + t1 w1 once each (contracted); the fmaf calls
-// reproduce that, so the resampled values are its values bit for bit (a separate rounding is 1 ulp of src -- up to 3e-5 of a
-// weight at 1080p -- away on ~1 % of pixels).
-__device__ inline void ms_source_taps(float scale, int dst, int in_size, int& i0, int& i1, float& l0, float& l1)
-{
-    float src = fmaf(scale, (float)dst + 0.5f, -0.5f);   // area_pixel_compute_source_index
-    src = src < 0.f ? 0.f : src;
-    const int idx = min((int)floorf(src), in_size - 1);  // guard_index_and_lambda
-    const float lam = fminf(fmaxf(src - (float)idx, 0.f), 1.f);
-    i0 = idx;
-    i1 = idx + (idx < in_size - 1 ? 1 : 0);
-    l1 = lam;
-    l0 = 1.f - lam;
-}
-
-__device__ inline float ms_bit(const uint64_t* __restrict__ row, int x) { return (float)((row[x >> 6] >> (x & 63)) & 1ull); }
-
+// pm_source_taps (packed_masks.h) states the rounding that makes the resampled values PyTorch's bit for bit.
 __global__ void __launch_bounds__(MS_THREADS) ms_erode_resample_kernel(int M, int h, int w, int Wqi, const uint64_t* __restrict__ in,
                                                                        int H, int W, int Wq, float scale_h, float scale_w,
                                                                        float min_sum, uint64_t* __restrict__ out)
@@ -111,7 +89,7 @@ __global__ void __launch_bounds__(MS_THREADS) ms_erode_resample_kernel(int M, in
             if (Y < 0 || Y >= H) continue;
             int sy0, sy1;
             float wy0, wy1;
-            ms_source_taps(scale_h, Y, h, sy0, sy1, wy0, wy1);
+            pm_source_taps(scale_h, Y, h, sy0, sy1, wy0, wy1);
             const uint64_t* r0 = plane + (size_t)sy0 * Wqi;
             const uint64_t* r1 = plane + (size_t)sy1 * Wqi;
             for (int dx = -1; dx <= 1; dx++) {
@@ -119,10 +97,10 @@ __global__ void __launch_bounds__(MS_THREADS) ms_erode_resample_kernel(int M, in
                 if (X < 0 || X >= W) continue;
                 int sx0, sx1;
                 float wx0, wx1;
-                ms_source_taps(scale_w, X, w, sx0, sx1, wx0, wx1);
+                pm_source_taps(scale_w, X, w, sx0, sx1, wx0, wx1);
                 // the reference's order: the width pass inside, the height pass outside
-                const float t0 = ms_bit(r0, sx0) * wx0 + ms_bit(r0, sx1) * wx1;
-                const float t1 = ms_bit(r1, sx0) * wx0 + ms_bit(r1, sx1) * wx1;
+                const float t0 = (float)pm_bit(r0, sx0) * wx0 + (float)pm_bit(r0, sx1) * wx1;
+                const float t1 = (float)pm_bit(r1, sx0) * wx0 + (float)pm_bit(r1, sx1) * wx1;
                 box += fmaf(t0, wy0, t1 * wy1);
             }
         }
@@ -148,12 +126,12 @@ __global__ void __launch_bounds__(MS_THREADS) ms_resize_kernel(int M, int h, int
     if (x < W) {
         int sy0, sy1, sx0, sx1;
         float wy0, wy1, wx0, wx1;
-        ms_source_taps(scale_h, y, h, sy0, sy1, wy0, wy1);
-        ms_source_taps(scale_w, x, w, sx0, sx1, wx0, wx1);
+        pm_source_taps(scale_h, y, h, sy0, sy1, wy0, wy1);
+        pm_source_taps(scale_w, x, w, sx0, sx1, wx0, wx1);
         const uint64_t* r0 = in + ((size_t)m * h + sy0) * Wqi;
         const uint64_t* r1 = in + ((size_t)m * h + sy1) * Wqi;
-        const float t0 = ms_bit(r0, sx0) * wx0 + ms_bit(r0, sx1) * wx1;
-        const float t1 = ms_bit(r1, sx0) * wx0 + ms_bit(r1, sx1) * wx1;
+        const float t0 = (float)pm_bit(r0, sx0) * wx0 + (float)pm_bit(r0, sx1) * wx1;
+        const float t1 = (float)pm_bit(r1, sx0) * wx0 + (float)pm_bit(r1, sx1) * wx1;
         bit = fmaf(t0, wy0, t1 * wy1) > threshold;
     }
     const uint64_t word = __ballot(bit);
@@ -194,7 +172,7 @@ __global__ void __launch_bounds__(64) ms_moments_kernel(int M, int H, int W, int
     }
 #pragma unroll
     for (int k = 0; k < MS_STATS; k++) tot[k] = wave_sum(tot[k]);
-    const uint64_t valid = ms_valid_bits(W, q);
+    const uint64_t valid = pm_valid_bits(W, q);
     const uint64_t all_rows = (1ull << rows) - 1ull;   // rows <= MS_TILE_ROWS < 64
     for (int m = 0; m < M; m++) {
         const uint64_t wd = lane < rows ? eroded[((size_t)m * H + y0 + lane) * Wq + q] : 0ull;   // lane r: the word of row y0 + r

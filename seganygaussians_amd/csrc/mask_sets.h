@@ -19,9 +19,7 @@
 #pragma once
 
 #include "../../include/mi_mask_scales.h"
-
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "packed_masks.h"
 
 namespace mirast {
 
@@ -182,6 +180,7 @@ __global__ void __launch_bounds__(MSET_BOX_THREADS) mset_boxes_kernel(int H, int
 
 // ---- NMS decision ----------------------------------------------------------------------------------------------------------------
 constexpr int MSET_NMS_MAX = 1024;   // one workgroup: a lane per mask
+static_assert(MSET_NMS_MAX == PM_MAX_MASKS, "every set of packed masks fits the one workgroup");
 
 // torch.max over a column: a NaN entry makes the maximum NaN
 __device__ inline float mset_nanmax(float cur, float v) { return (v > cur || v != v) ? v : cur; }

@@ -1,7 +1,6 @@
 // mi_clip_tiles.hip -- C-ABI implementation of the CLIP-tiles section of include/mi_mask_scales.h (mi_mask_resize is in
 // mi_mask_scales.hip, beside the erosion whose taps it shares).
 #include "host.h"
-#include "../../include/mi_contrastive.h"   // MI_CONTRASTIVE_LOSS_MAX_MASKS
 #include "../../include/mi_mask_scales.h"
 
 #include "clip_tiles.h"   // masked crops resized and normalised for the CLIP network, and the mask index map
@@ -11,10 +10,8 @@ using namespace mirast;
 namespace {
 int ct_check(int M, int H, int W)
 {
-    if (M < 1 || M > MI_CONTRASTIVE_LOSS_MAX_MASKS || H < 1 || W < 1)
-        return fail(MI_RAST_ERR_INVALID, "clip tiles: need 1 <= M <= 1024 masks and H, W >= 1");
-    if ((size_t)H * (size_t)W >= ((size_t)1 << 24)) return fail(MI_RAST_ERR_INVALID, "clip tiles: need H * W < 2^24 pixels");
-    return MI_RAST_OK;
+    if (int rc = pm_check_dims("clip tiles", M, H, W)) return rc;
+    return pm_pixels_ok(H, W) ? MI_RAST_OK : fail(MI_RAST_ERR_INVALID, "clip tiles: need H * W < 2^24 pixels");
 }
 
 template <bool AA, typename OutT>
@@ -22,7 +19,7 @@ void ct_launch(int M, int H, int W, const uint64_t* packed, const uint8_t* image
                const CtNorm& nrm, int Sh, int Sw, void* tiles, hipStream_t stream)
 {
     hipLaunchKernelGGL((ct_tiles_kernel<AA, OutT>), dim3((unsigned)((Sh + CT_BAND - 1) / CT_BAND), (unsigned)M), dim3(CT_THREADS), 0,
-                       stream, H, W, (W + 63) / 64, packed, image, rects, layout, bg, nrm, Sh, Sw, (OutT*)tiles);
+                       stream, H, W, pm_row_words(W), packed, image, rects, layout, bg, nrm, Sh, Sw, (OutT*)tiles);
 }
 }  // namespace
 
@@ -67,12 +64,12 @@ int mi_mask_index_map(int M, int H, int W, const unsigned long long* packed, int
 {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = ct_check(M, H, W)) return rc;
-    if (offset < 0 || offset > 0x7fffffff - MI_CONTRASTIVE_LOSS_MAX_MASKS)
+    if (offset < 0 || offset > 0x7fffffff - PM_MAX_MASKS)
         return fail(MI_RAST_ERR_INVALID, "mask index map: need 0 <= offset <= 2^31 - 1 - 1024");
     if (!packed || !out) return fail(MI_RAST_ERR_INVALID, "clip tiles: null pointer");
-    const size_t NW = (size_t)H * ((W + 63) / 64);
+    const size_t NW = pm_words(1, H, W);   // one wave per word of the image
     constexpr int wpb = CT_THREADS / 64;
-    hipLaunchKernelGGL(ct_index_map_kernel, dim3((unsigned)((NW + wpb - 1) / wpb)), dim3(CT_THREADS), 0, stream, M, H, W, (W + 63) / 64,
+    hipLaunchKernelGGL(ct_index_map_kernel, dim3((unsigned)((NW + wpb - 1) / wpb)), dim3(CT_THREADS), 0, stream, M, H, W, pm_row_words(W),
                        (const uint64_t*)packed, offset, out);
     HIP_TRY(hipGetLastError());
     return MI_RAST_OK;

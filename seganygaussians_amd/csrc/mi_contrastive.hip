@@ -72,12 +72,6 @@ int mi_contrastive_backward(int C, int h, int w, const float* rendered, int H, i
 
 // ---- contrastive loss: SAM-mask targets and the pair loss (mi_contrastive.h, contrastive_loss.h) ------------------------------
 namespace {
-int cl_check_masks(int M, int H, int W)
-{
-    if (M < 1 || M > MI_CONTRASTIVE_LOSS_MAX_MASKS || H < 1 || W < 1)
-        return fail(MI_RAST_ERR_INVALID, "contrastive loss: need 1 <= M <= 1024 masks and H, W >= 1");
-    return MI_RAST_OK;
-}
 int cl_check_loss(int S, int N, int C, int M)
 {
     if (S < 0 || N < 1 || N > MI_CONTRASTIVE_LOSS_MAX_SCALES || C < 1 || C > 256 || M < 1 || M > MI_CONTRASTIVE_LOSS_MAX_MASKS)
@@ -90,11 +84,10 @@ int cl_check_loss(int S, int N, int C, int M)
 int mi_contrastive_pack_masks(int M, int H, int W, const unsigned char* masks, unsigned long long* packed, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = cl_check_masks(M, H, W)) return rc;
+    if (int rc = pm_check_dims("contrastive loss", M, H, W)) return rc;
     if (!masks || !packed) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
-    const int Wq = (W + 63) / 64;
-    const size_t words = (size_t)M * H * Wq;
-    hipLaunchKernelGGL(cl_pack_kernel, dim3((unsigned)((words + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, stream, M, H, W, Wq,
+    const size_t words = pm_words(M, H, W);
+    hipLaunchKernelGGL(cl_pack_kernel, dim3((unsigned)((words + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, stream, M, H, W, pm_row_words(W),
                        (const uint8_t*)masks, (uint64_t*)packed);
     HIP_TRY(hipGetLastError());
     return MI_RAST_OK;
@@ -104,9 +97,9 @@ int mi_contrastive_cover(int M, int H, int W, const unsigned long long* packed, 
                          unsigned char* sampled_ray, unsigned long long* acc, void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = cl_check_masks(M, H, W)) return rc;
+    if (int rc = pm_check_dims("contrastive loss", M, H, W)) return rc;
     if (!packed || !ray_rand || !sampled_ray || !acc) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
-    const int Wq = (W + 63) / 64;
+    const int Wq = pm_row_words(W);
     const size_t words = (size_t)H * Wq;
     hipLaunchKernelGGL(cl_cover_kernel, dim3((unsigned)((words + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, stream, M, H, W, Wq,
                        (const uint64_t*)packed, ray_rand, rate, (uint8_t*)sampled_ray, acc + CL_ACC_AREA);
@@ -119,12 +112,12 @@ int mi_contrastive_targets(int M, int H, int W, const unsigned long long* packed
                            void* stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = cl_check_masks(M, H, W)) return rc;
+    if (int rc = pm_check_dims("contrastive loss", M, H, W)) return rc;
     if (int rc = cl_check_loss(S, N, 1, M)) return rc;
     if (!packed || !sort_idx || !scale_si || !scale_ub || !acc) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null pointer");
     if (S == 0) return MI_RAST_OK;
     if (!ray_yx || !gt || !a) return fail(MI_RAST_ERR_INVALID, "contrastive loss: null ray buffers");
-    const int Wq = (W + 63) / 64, Wd = (M + 63) / 64;
+    const int Wq = pm_row_words(W), Wd = (M + 63) / 64;
     hipLaunchKernelGGL(cl_targets_kernel, dim3((unsigned)(((size_t)S * 64 + CL_THREADS - 1) / CL_THREADS)), dim3(CL_THREADS), 0, stream,
                        M, H, Wq, (const uint64_t*)packed, (const int64_t*)sort_idx, S, ray_yx, N, scale_si, scale_ub, Wd, (uint64_t*)gt, a, acc);
     hipLaunchKernelGGL(cl_classes_kernel, dim3((unsigned)S), dim3(CL_THREADS), 0, stream, S, N, Wd, (const uint64_t*)gt, acc);

@@ -1,6 +1,5 @@
 // mi_mask_sets.hip -- C-ABI implementation of the mask-sets section of include/mi_mask_scales.h.
 #include "host.h"
-#include "../../include/mi_contrastive.h"   // MI_CONTRASTIVE_LOSS_MAX_MASKS
 #include "../../include/mi_mask_scales.h"
 
 #include "mask_sets.h"   // set operations on packed SAM masks: overlaps, boxes, NMS decision, score images
@@ -10,17 +9,14 @@ using namespace mirast;
 namespace {
 int mset_check(int M, int H, int W)
 {
-    if (M < 1 || M > MI_CONTRASTIVE_LOSS_MAX_MASKS || H < 1 || W < 1)
-        return fail(MI_RAST_ERR_INVALID, "mask sets: need 1 <= M <= 1024 masks and H, W >= 1");
-    if ((size_t)H * (size_t)W >= ((size_t)1 << 24))
-        return fail(MI_RAST_ERR_INVALID, "mask sets: need H * W < 2^24 pixels (every count is then exact in f32)");
-    return MI_RAST_OK;
+    if (int rc = pm_check_dims("mask sets", M, H, W)) return rc;
+    return pm_pixels_ok(H, W) ? MI_RAST_OK : fail(MI_RAST_ERR_INVALID, "mask sets: need H * W < 2^24 pixels (every count is then exact in f32)");
 }
 
 template <int MODE>
 void mset_launch_images(int M, int H, int W, int K, const uint64_t* packed, const float* scores, float* out, hipStream_t stream)
 {
-    const int Wq = (W + 63) / 64;
+    const int Wq = pm_row_words(W);
     const size_t NW = (size_t)H * Wq;
     const dim3 grid((unsigned)((NW + MSET_SI_WORDS - 1) / MSET_SI_WORDS)), block(MSET_SI_THREADS);
     if (K == 1)
@@ -42,7 +38,7 @@ int mi_mask_overlaps(int M, int H, int W, const unsigned long long* packed, cons
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = mset_check(M, H, W)) return rc;
     if (!packed || !inter) return fail(MI_RAST_ERR_INVALID, "mask sets: null pointer");
-    const size_t NW = (size_t)H * ((W + 63) / 64);
+    const size_t NW = (size_t)H * pm_row_words(W);
     const int T = (M + MSET_OV_TILE - 1) / MSET_OV_TILE, tiles = mset_upper_tiles(T);
     // slices of the words, whole chunks each, so that tiles x slices gives every CU the three workgroups its registers admit at
     // small M (the kernel is bound by its vector popcounts, so it wants the waves); more slices would only add atomics
@@ -64,7 +60,7 @@ int mi_mask_boxes(int M, int H, int W, const unsigned long long* packed, float* 
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = mset_check(M, H, W)) return rc;
     if (!packed || !boxes) return fail(MI_RAST_ERR_INVALID, "mask sets: null pointer");
-    hipLaunchKernelGGL(mset_boxes_kernel, dim3((unsigned)M), dim3(MSET_BOX_THREADS), 0, stream, H, (W + 63) / 64,
+    hipLaunchKernelGGL(mset_boxes_kernel, dim3((unsigned)M), dim3(MSET_BOX_THREADS), 0, stream, H, pm_row_words(W),
                        (const uint64_t*)packed, boxes, areas);
     HIP_TRY(hipGetLastError());
     return MI_RAST_OK;

@@ -1,19 +1,17 @@
 // mi_vote_graph.hip -- C-ABI implementation of the vote-graph section of include/mi_segment.h.
 #include "host.h"
-#include "../../include/mi_contrastive.h"   // MI_CONTRASTIVE_LOSS_MAX_MASKS
 #include "../../include/mi_segment.h"
 
+#include "packed_masks.h"  // the layout of the eroded masks
 #include "vote_graph.h"    // language-segmentation vote graph: mask features, anchor bits, relevancy
 
 using namespace mirast;
 
 namespace {
-size_t vg_tiles(int h, int w) { return (size_t)((h + VG_TILE_ROWS - 1) / VG_TILE_ROWS) * ((w + 63) / 64); }
-
 bool vg_mask_sizes_ok(int M, int C, int h, int w)
 {
-    return M >= 1 && M <= MI_CONTRASTIVE_LOSS_MAX_MASKS && C >= 1 && C <= MI_SEGMENT_MAX_CHANNELS && h >= 1 && w >= 1 &&
-           (size_t)C * h * w < ((size_t)1 << 31) && (size_t)M * h * ((w + 63) / 64) < ((size_t)1 << 31);
+    return M >= 1 && M <= PM_MAX_MASKS && C >= 1 && C <= MI_SEGMENT_MAX_CHANNELS && h >= 1 && w >= 1 &&
+           (size_t)C * h * w < ((size_t)1 << 31) && pm_words(M, h, w) < ((size_t)1 << 31);
 }
 }  // namespace
 
@@ -24,8 +22,8 @@ size_t mi_vote_mask_features_workspace_bytes(int M, int C, int h, int w)
     if (!vg_mask_sizes_ok(M, C, h, w)) return 0;
     Carver cv;
     cv.take((size_t)C * h * w * sizeof(float));
-    cv.take((size_t)M * vg_tiles(h, w) * sizeof(double));
-    cv.take((size_t)M * vg_tiles(h, w) * C * sizeof(double));
+    cv.take((size_t)M * pm_tiles(h, w, VG_TILE_ROWS) * sizeof(double));
+    cv.take((size_t)M * pm_tiles(h, w, VG_TILE_ROWS) * C * sizeof(double));
     return cv.off;
 }
 
@@ -39,7 +37,7 @@ int mi_vote_mask_features(int M, int C, int H, int W, const float* rendered, int
     if (workspace_bytes < mi_vote_mask_features_workspace_bytes(M, C, h, w))
         return fail(MI_RAST_ERR_INVALID, "vote graph: workspace smaller than mi_vote_mask_features_workspace_bytes(M, C, h, w)");
     if ((uintptr_t)workspace % 8) return fail(MI_RAST_ERR_INVALID, "vote graph: the workspace must be 8-byte aligned");
-    const size_t T = vg_tiles(h, w);
+    const size_t T = pm_tiles(h, w, VG_TILE_ROWS);
     Carver cv;
     char* base = (char*)workspace;
     float* fs = (float*)(base + cv.take((size_t)C * h * w * sizeof(float)));
@@ -48,7 +46,7 @@ int mi_vote_mask_features(int M, int C, int H, int W, const float* rendered, int
     const size_t n = (size_t)C * h * w;
     hipLaunchKernelGGL(vg_resample_kernel, dim3((unsigned)((n + VG_THREADS - 1) / VG_THREADS)), dim3(VG_THREADS), 0, stream, C, H, W,
                        rendered, h, w, (double)H / (double)h, (double)W / (double)w, fs);
-    hipLaunchKernelGGL(vg_mask_sums_kernel, dim3((unsigned)T, (unsigned)((M + VG_MASK_GROUP - 1) / VG_MASK_GROUP)), dim3(64), 0, stream, M, C, h, w, (w + 63) / 64, (const uint64_t*)eroded,
+    hipLaunchKernelGGL(vg_mask_sums_kernel, dim3((unsigned)T, (unsigned)((M + VG_MASK_GROUP - 1) / VG_MASK_GROUP)), dim3(64), 0, stream, M, C, h, w, pm_row_words(w), (const uint64_t*)eroded,
                        (const float*)fs, gates, (int)T, tile_counts, tile_sums);
     hipLaunchKernelGGL(vg_mask_finalize_kernel, dim3((unsigned)M), dim3(VG_THREADS), 0, stream, C, (int)T, (const double*)tile_counts,
                        (const double*)tile_sums, gates, features, counts);

@@ -19,47 +19,7 @@ import torch
 
 from ._args import f32, number, size_hw
 from ._ffi import check, stream_ptr
-from .contrastive_loss import MAX_MASKS, PackedSamMasks, pack_sam_masks
-
-MAX_PIXELS = 1 << 24
-
-
-def check_shape(who: str, masks) -> None:
-    """The limits of sam_masks.py and clip_tiles.py that need no device, before anything is packed or launched (the rest is
-    as_packed's)."""
-    if not isinstance(masks, PackedSamMasks) and not (isinstance(masks, torch.Tensor) and masks.dtype == torch.bool and masks.dim() == 3):
-        raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got "
-                         f"{getattr(masks, 'dtype', type(masks))} {tuple(getattr(masks, 'shape', ()))}")
-    M, h, w = (int(v) for v in masks.shape)
-    if not 1 <= M <= MAX_MASKS:
-        raise ValueError(f"{who}: need 1 <= M <= {MAX_MASKS} masks, got {M}")
-    if h * w >= MAX_PIXELS:
-        raise ValueError(f"{who}: need h * w < 2^24 pixels, got {h} x {w}")
-
-
-def as_packed(who: str, masks, dev, versus: str = "depth") -> PackedSamMasks:
-    """masks as a PackedSamMasks on the GPU dev (None: on their own GPU, or the current one for CPU masks).  versus names the
-    tensor whose GPU dev is, for the message about masks that are elsewhere."""
-    if isinstance(masks, PackedSamMasks):
-        M, h, w = masks.shape
-        words = masks.words
-        if not 1 <= M <= MAX_MASKS or h < 1 or w < 1:
-            raise ValueError(f"{who}: need 1 <= M <= {MAX_MASKS} masks and a non-empty image, got {(M, h, w)}")
-        if words.dtype != torch.int64 or tuple(words.shape) != (M, h, (w + 63) // 64) or not words.is_cuda:
-            raise ValueError(f"{who}: PackedSamMasks words must be int64 ({M}, {h}, {(w + 63) // 64}) on a GPU, got "
-                             f"{words.dtype} {tuple(words.shape)} on {words.device}")
-        if dev is not None and words.device != dev:
-            raise ValueError(f"{who}: the masks are on {words.device}, the {versus} on {dev}")
-        return PackedSamMasks(words.contiguous(), (M, h, w))
-    if isinstance(masks, torch.Tensor):
-        if masks.dtype != torch.bool or masks.dim() != 3:
-            raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got {masks.dtype} {tuple(masks.shape)}")
-        if masks.is_cuda and dev is not None and masks.device != dev:
-            raise ValueError(f"{who}: the masks are on {masks.device}, the {versus} on {dev}")
-        if not masks.is_cuda and masks.device.type != "cpu":
-            raise ValueError(f"{who}: masks on {masks.device}; need the CPU or a GPU")
-        return pack_sam_masks(masks, device=dev)   # checks M and the image size
-    raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got {type(masks)}")
+from .packed_masks import MAX_MASKS, MAX_PIXELS, PackedSamMasks, as_packed, check_shape, pack_sam_masks, row_words  # noqa: F401
 
 
 def erode(packed: PackedSamMasks, H: int, W: int, min_sum: float = 5.0) -> PackedSamMasks:
@@ -67,9 +27,9 @@ def erode(packed: PackedSamMasks, H: int, W: int, min_sum: float = 5.0) -> Packe
     L = _lib.load()
     M, h, w = packed.shape
     dev = packed.device
-    if M * H * ((W + 63) // 64) >= 1 << 31 or M * h * ((w + 63) // 64) >= 1 << 31:
+    if M * H * row_words(W) >= 1 << 31 or M * h * row_words(w) >= 1 << 31:
         raise ValueError("erode_sam_masks: more than 2^31 mask words")
-    out = torch.empty((M, H, (W + 63) // 64), device=dev, dtype=torch.int64)
+    out = torch.empty((M, H, row_words(W)), device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
         check(L.mi_mask_erode_min_sum(M, h, w, packed.words.data_ptr(), H, W, min_sum, out.data_ptr(), stream_ptr(dev)))
     return PackedSamMasks(out, (M, H, W))
@@ -115,7 +75,7 @@ def sam_mask_scales(depth: torch.Tensor, masks, fovx: float, fovy: float, return
     dev = depth.device
     packed = as_packed("sam_mask_scales", masks, dev)
     M = packed.shape[0]
-    if M * H * ((W + 63) // 64) >= 1 << 31:
+    if M * H * row_words(W) >= 1 << 31:
         raise ValueError("sam_mask_scales: more than 2^31 mask words")
     # :138-139 in float64 (numpy's tan of the Python floats FoVx / FoVy)
     fx = (W / 2) / math.tan(fovx / 2)

@@ -23,8 +23,7 @@ import torch
 from . import _lib
 from ._args import check_out, f32, number, size_hw
 from ._ffi import check, stream_ptr
-from .contrastive_loss import MAX_MASKS, PackedSamMasks
-from .mask_scales import MAX_PIXELS, as_packed, check_shape
+from .packed_masks import MAX_MASKS, MAX_PIXELS, PackedSamMasks, as_packed, check_shape, row_words
 
 MAX_SCORE_COLUMNS = _lib.MI_MASK_SCORE_MAX_COLUMNS
 
@@ -190,7 +189,7 @@ def resize_sam_masks(masks, size, threshold=0.5) -> PackedSamMasks:
     packed = _packed(masks, None, "resize_sam_masks")
     M, h, w = packed.shape
     dev = packed.device
-    out = torch.empty((M, H, (W + 63) // 64), device=dev, dtype=torch.int64)
+    out = torch.empty((M, H, row_words(W)), device=dev, dtype=torch.int64)
     with torch.cuda.device(dev):
         check(_lib.load().mi_mask_resize(M, h, w, packed.words.data_ptr(), H, W, threshold, out.data_ptr(), stream_ptr(dev)))
     return PackedSamMasks(out, (M, H, W))

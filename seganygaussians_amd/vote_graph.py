@@ -19,8 +19,8 @@ from . import _lib
 from ._args import f32, no_grad_one_gpu, number, size_hw
 from ._ffi import check, stream_ptr
 from .clustering import MAX_POINTS
-from .contrastive_loss import MAX_MASKS, PackedSamMasks
-from .mask_scales import as_packed, erode
+from .mask_scales import erode
+from .packed_masks import as_packed, mask_dims, row_words
 
 MAX_CHANNELS = 256
 MAX_ANCHORS = _lib.MI_VOTE_MAX_ANCHORS     # 32 MI_CLUSTER_MAX_WORDS
@@ -60,19 +60,11 @@ def sam_mask_features(rendered: torch.Tensor, masks, gates: torch.Tensor, size=N
     if C * h * w >= 1 << 31:
         raise ValueError(f"{who}: more than 2^31 values at the working resolution {(h, w)}")
     min_sum = number(who, "min_sum", min_sum)
-    if isinstance(masks, PackedSamMasks):
-        M = int(masks.shape[0])
-    elif isinstance(masks, torch.Tensor) and masks.dtype == torch.bool and masks.dim() == 3:
-        M = int(masks.shape[0])
-    else:
-        raise ValueError(f"{who}: masks must be a bool (M, h, w) tensor or PackedSamMasks, got "
-                         f"{getattr(masks, 'dtype', type(masks))} {tuple(getattr(masks, 'shape', ()))}")
-    if not 1 <= M <= MAX_MASKS:
-        raise ValueError(f"{who}: need 1 <= M <= {MAX_MASKS} masks, got {M}")
+    M = mask_dims(who, masks)[0]   # not check_shape: the masks' own size has no pixel limit here
     _f32_matrix(who, "gates", gates, M, C)
     dev = no_grad_one_gpu(who, [("rendered", rendered), ("gates", gates)])
     packed = as_packed(who, masks, dev)
-    if M * h * ((w + 63) // 64) >= 1 << 31:
+    if M * h * row_words(w) >= 1 << 31:
         raise ValueError(f"{who}: more than 2^31 mask words")
     L = _lib.load()
     rendered, gates = rendered.detach().contiguous(), gates.detach().contiguous()

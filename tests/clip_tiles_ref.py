@@ -151,8 +151,8 @@ def aa_weights(n_in, n_out):
 
 
 def linear_weights(n_in, n_out):
-    """upsample_bilinear2d's two taps (align_corners=False) as ATen computes them for float32 -- ms_source_taps of
-    csrc/mask_scales.h: src = max(fma(scale, dst + 0.5, -0.5), 0).  (The product of two float32 numbers, one of them a small integer
+    """upsample_bilinear2d's two taps (align_corners=False) as ATen computes them for float32 -- pm_source_taps of
+    csrc/packed_masks.h: src = max(fma(scale, dst + 0.5, -0.5), 0).  (The product of two float32 numbers, one of them a small integer
     + 0.5, minus 0.5 is exact in float64, so one rounding of the float64 result is the fused operation.)  The same list form as
     aa_weights: (i0, [l0, l1]), or (i0, [l0 + l1]) where the two taps coincide."""
     scale = F32(n_in) / F32(n_out)

@@ -170,7 +170,8 @@ def multi_res_check(name, F, levels, w, g, normalize_out, out, dF, dw):
 
 def taps_f32(n_out: int, n_in: int):
     """Lower tap, upper tap and upper weight of every output index of a bilinear resize n_in -> n_out with align_corners=False, AS
-    ATen COMPUTES THEM FOR FLOAT32 INPUT (area_pixel_compute_source_index; bilinear_tap of csrc/contrastive.h):
+    ATen COMPUTES THEM FOR FLOAT32 INPUT (area_pixel_compute_source_index; bilinear_tap of csrc/contrastive.h, which stays beside
+    pm_source_taps of csrc/packed_masks.h: the same source index, lam not clamped):
     scale = float32(n_in) / float32(n_out), src = max(fma(dst + 0.5, scale, -0.5), 0) -- ATen's builds contract the multiply and
     the subtraction into one fused operation -- and lam = src - i0, rounded to float32.  (The product of two float32 numbers, one of
     them a small integer + 0.5, minus 0.5 is exact in float64, so one rounding of the float64 result is the fused operation.)

@@ -155,7 +155,7 @@ def test_one_set_of_call_helpers():
     assert set(shared) == {"check", "ptr", "dev_ptr", "contig", "stream_ptr"}
     for name in ("knn", "contrastive_loss", "contrastive_frontend", "segmentation", "photometric", "mask_scales", "knn_smooth",
                  "rasterizer", "geometry_cache", "sam_masks", "clip_tiles", "viewer", "vote_graph", "clustering", "lifting",
-                 "training_step"):
+                 "training_step", "packed_masks"):
         mod = importlib.import_module("seganygaussians_amd." + name)
         for attr, value in vars(mod).items():
             assert attr not in ("_check", "_ptr", "_stream", "_stream_ptr", "_dev_ptr", "_contig"), f"{name}.{attr}"
@@ -174,7 +174,7 @@ def test_one_set_of_argument_checks():
     assert shared == {"to_float", "number", "f32", "size_hw", "no_grad_one_gpu", "check_out"}
     assert not any(isinstance(v, types.ModuleType) and v.__name__.startswith("seganygaussians_amd") for v in vars(_args).values())
     for name in ("segmentation", "photometric", "mask_scales", "clustering", "lifting", "vote_graph", "knn_smooth", "sam_masks",
-                 "clip_tiles", "viewer"):
+                 "clip_tiles", "viewer", "packed_masks"):
         mod = importlib.import_module("seganygaussians_amd." + name)
         for attr, value in vars(mod).items():
             if attr.startswith("_") and isinstance(value, types.FunctionType):

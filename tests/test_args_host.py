@@ -1,13 +1,12 @@
-"""The argument checks the feature modules share (_args.py; the feature-table pieces in segmentation.py; the mask pieces in
-mask_scales.py), called directly: what each accepts and returns, and the exact text of each refusal.  CPU-only; a GPU tensor is
+"""The argument checks the feature modules share (_args.py; the feature-table pieces in segmentation.py; the mask pieces are in
+test_packed_masks_host.py), called directly: what each accepts and returns, and the exact text of each refusal.  CPU-only; a GPU tensor is
 stood in for by a CPU tensor whose is_cuda and device say otherwise."""
 import re
 
 import pytest
 import torch
 
-from seganygaussians_amd import _args, mask_scales, segmentation
-from seganygaussians_amd.contrastive_loss import PackedSamMasks
+from seganygaussians_amd import _args, segmentation
 
 
 def on_gpu(t, device="cuda:0"):
@@ -153,63 +152,3 @@ def test_gate_row_and_check_pre():
         segmentation.check_pre("f", "L2")
     with refuses("f: pre must be one of ['eps', 'l2', 'none'], got None"):
         segmentation.check_pre("f", None)
-
-
-def test_check_shape():
-    assert mask_scales.check_shape("f", torch.zeros(3, 4, 6, dtype=torch.bool)) is None
-    assert mask_scales.check_shape("f", PackedSamMasks(torch.zeros(3, 4, 1, dtype=torch.int64), (3, 4, 6))) is None
-    with refuses("f: masks must be a bool (M, h, w) tensor or PackedSamMasks, got torch.float32 (3, 4, 6)"):
-        mask_scales.check_shape("f", torch.zeros(3, 4, 6))
-    with refuses("f: masks must be a bool (M, h, w) tensor or PackedSamMasks, got torch.bool (4, 6)"):
-        mask_scales.check_shape("f", torch.zeros(4, 6, dtype=torch.bool))
-    with refuses("f: masks must be a bool (M, h, w) tensor or PackedSamMasks, got <class 'NoneType'> ()"):
-        mask_scales.check_shape("f", None)
-    with refuses("f: need 1 <= M <= 1024 masks, got 0"):
-        mask_scales.check_shape("f", torch.zeros(0, 4, 6, dtype=torch.bool))
-    with refuses("f: need 1 <= M <= 1024 masks, got 1025"):
-        mask_scales.check_shape("f", PackedSamMasks(None, (1025, 1, 1)))
-    with refuses("f: need h * w < 2^24 pixels, got 4096 x 4096"):
-        mask_scales.check_shape("f", PackedSamMasks(None, (1, 4096, 4096)))
-
-
-def test_as_packed(monkeypatch):
-    dev = torch.device("cuda:0")
-    i64 = lambda *shape: torch.zeros(shape, dtype=torch.int64)
-    words = on_gpu(i64(3, 4, 1))
-    for d in (None, dev):
-        got = mask_scales.as_packed("f", PackedSamMasks(words, (3, 4, 6)), d)
-        assert isinstance(got, PackedSamMasks) and got.words.data_ptr() == words.data_ptr() and got.shape == (3, 4, 6)
-    # masks on another GPU than the tensor they go with, under each of its three names (and the default)
-    elsewhere = PackedSamMasks(on_gpu(i64(3, 4, 1), "cuda:1"), (3, 4, 6))
-    with refuses("f: the masks are on cuda:1, the depth on cuda:0"):
-        mask_scales.as_packed("f", elsewhere, dev)
-    for versus in ("depth", "scores", "image"):
-        with refuses(f"f: the masks are on cuda:1, the {versus} on cuda:0"):
-            mask_scales.as_packed("f", elsewhere, dev, versus)
-    masks = torch.zeros(3, 4, 6, dtype=torch.bool)
-    for versus in ("depth", "scores", "image"):
-        with refuses(f"f: the masks are on cuda:1, the {versus} on cuda:0"):
-            mask_scales.as_packed("f", on_gpu(masks, "cuda:1"), dev, versus)
-    # a bool tensor goes to pack_sam_masks with the device
-    seen = []
-    monkeypatch.setattr(mask_scales, "pack_sam_masks", lambda m, device=None: seen.append((m, device)) or "packed")
-    assert mask_scales.as_packed("f", masks, dev) == "packed" and seen[0][0] is masks and seen[0][1] == dev
-    assert mask_scales.as_packed("f", on_gpu(masks, "cuda:1"), None) == "packed" and seen[1][1] is None
-    with refuses("f: need 1 <= M <= 1024 masks and a non-empty image, got (3, 0, 6)"):
-        mask_scales.as_packed("f", PackedSamMasks(words, (3, 0, 6)), dev)
-    with refuses("f: need 1 <= M <= 1024 masks and a non-empty image, got (1025, 4, 6)"):
-        mask_scales.as_packed("f", PackedSamMasks(words, (1025, 4, 6)), dev)
-    with refuses("f: PackedSamMasks words must be int64 (3, 4, 1) on a GPU, got torch.int64 (3, 4, 2) on cuda:0"):
-        mask_scales.as_packed("f", PackedSamMasks(on_gpu(i64(3, 4, 2)), (3, 4, 6)), dev)
-    with refuses("f: PackedSamMasks words must be int64 (3, 4, 1) on a GPU, got torch.int32 (3, 4, 1) on cuda:0"):
-        mask_scales.as_packed("f", PackedSamMasks(on_gpu(i64(3, 4, 1).int()), (3, 4, 6)), dev)
-    with refuses("f: PackedSamMasks words must be int64 (3, 4, 1) on a GPU, got torch.int64 (3, 4, 1) on cpu"):
-        mask_scales.as_packed("f", PackedSamMasks(torch.zeros(3, 4, 1, dtype=torch.int64), (3, 4, 6)), dev)
-    with refuses("f: masks must be a bool (M, h, w) tensor or PackedSamMasks, got torch.float32 (3, 4, 6)"):
-        mask_scales.as_packed("f", torch.zeros(3, 4, 6), dev)
-    with refuses("f: masks must be a bool (M, h, w) tensor or PackedSamMasks, got torch.bool (4, 6)"):
-        mask_scales.as_packed("f", torch.zeros(4, 6, dtype=torch.bool), dev)
-    with refuses("f: masks on meta; need the CPU or a GPU"):
-        mask_scales.as_packed("f", torch.zeros(3, 4, 6, dtype=torch.bool, device="meta"), dev)
-    with refuses("f: masks must be a bool (M, h, w) tensor or PackedSamMasks, got <class 'list'>"):
-        mask_scales.as_packed("f", [[True]], dev)
