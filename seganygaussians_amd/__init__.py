@@ -45,9 +45,20 @@ def install_dropin(fuse_smoothing: bool = False, fuse_training_step: bool = Fals
     return DROPIN_DIR
 
 
+def install_model_edit() -> None:
+    """Opt-in, a call of its own next to install_dropin: rebinds `segment`, `roll_back` and `clear_segment` of both
+    `scene.gaussian_model.GaussianModel` and `scene.gaussian_model_ff.FeatureGaussianModel` to the HIP cut (model_edit.py, DESIGN.md
+    section 26), at once for a module that is already imported, otherwise right after its import: same attributes maintained
+    (`old_*`, `_mask`, `segment_times`), one host read per cut.  The originals stay reachable as `_reference_*`; a model with an
+    optimizer runs the reference's own `segment`.  Idempotent; combines with install_dropin(fuse_smoothing=True) and
+    (fuse_training_step=True), which patch the same two modules, in any order."""
+    _patch_now_or_on_import(_GM_MODULE, "GaussianModel", patch_model_edit)
+    _patch_now_or_on_import(_FF_MODULE, "FeatureGaussianModel", patch_model_edit)
+
+
 # the viewer frame (viewer.py, DESIGN.md section 25), resolved on first use so that importing the package stays free of torch
 _VIEWER_NAMES = ("ViewerFrame", "feature_covariance", "feature_pca_basis", "gui_pca_sample", "prompt_features", "viewer_frame")
-__all__ = ["install_dropin", "patch_feature_model", "patch_gaussian_model"] + list(_VIEWER_NAMES)
+__all__ = ["install_dropin", "install_model_edit", "patch_feature_model", "patch_gaussian_model", "patch_model_edit"] + list(_VIEWER_NAMES)
 
 
 def __getattr__(name):
@@ -65,8 +76,13 @@ def _patch_now_or_on_import(module_name: str, class_name: str, patch) -> None:
     mod = sys.modules.get(module_name)
     if mod is not None and hasattr(mod, class_name):
         patch(getattr(mod, class_name))
-    elif not any(isinstance(f, _PatchOnImport) and f.module_name == module_name for f in sys.meta_path):
+        return
+    # one finder per module name, however many patches wait for that module and however often each is asked for
+    finder = next((f for f in sys.meta_path if isinstance(f, _PatchOnImport) and f.module_name == module_name), None)
+    if finder is None:
         sys.meta_path.insert(0, _PatchOnImport(module_name, class_name, patch))
+    elif (class_name, patch) not in finder.patches:
+        finder.patches.append((class_name, patch))
 
 
 def patch_feature_model(cls) -> None:
@@ -98,12 +114,24 @@ def patch_gaussian_model(cls) -> None:
     cls._mi_fused_training_step = True
 
 
+def patch_model_edit(cls) -> None:
+    """Rebinds segment, roll_back and clear_segment of cls (the reference's GaussianModel or FeatureGaussianModel) to the HIP cut
+    (model_edit.py); idempotent.  The originals stay reachable as cls._reference_<name>."""
+    if vars(cls).get("_mi_fused_model_edit", False):      # of cls itself: the patch serves two classes
+        return
+    from . import model_edit as me
+    for name, fn in (("segment", me.fused_segment), ("roll_back", me.fused_roll_back), ("clear_segment", me.fused_clear_segment)):
+        setattr(cls, "_reference_" + name, getattr(cls, name))
+        setattr(cls, name, fn)
+    cls._mi_fused_model_edit = True
+
+
 class _PatchOnImport:
-    """sys.meta_path finder: lets the normal machinery find `module_name`, then calls patch(module.<class_name>) once the
-    module has been executed."""
+    """sys.meta_path finder: lets the normal machinery find `module_name`, then calls patch(module.<class name>) for every
+    (class name, patch) pair of `patches` once the module has been executed."""
 
     def __init__(self, module_name: str = _FF_MODULE, class_name: str = "FeatureGaussianModel", patch=patch_feature_model):
-        self.module_name, self.class_name, self.patch = module_name, class_name, patch
+        self.module_name, self.patches = module_name, [(class_name, patch)]
 
     def find_spec(self, name, path=None, target=None):
         if name != self.module_name:
@@ -120,8 +148,9 @@ class _PatchOnImport:
 
         def exec_module(module, _inner=inner):
             _inner(module)
-            if hasattr(module, self.class_name):
-                self.patch(getattr(module, self.class_name))
+            for class_name, patch in self.patches:
+                if hasattr(module, class_name):
+                    patch(getattr(module, class_name))
             if self in sys.meta_path:
                 sys.meta_path.remove(self)
 

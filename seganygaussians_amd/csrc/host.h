@@ -1,5 +1,5 @@
 // host.h -- what the host files of the C-ABI library (mi_*.hip, one per public header) share: the calling thread's last error
-// (mi_rast_last_error), HIP_TRY, and the 256-byte carving of workspaces and state buffers.
+// (mi_rast_last_error), HIP_TRY, the 256-byte carving of workspaces and state buffers, and the overlap check of a call's byte ranges.
 #pragma once
 
 #include "../../include/mi_rast.h"
@@ -39,5 +39,26 @@ struct Carver {
         return o;
     }
 };
+
+// a byte range of a call's arguments, for the check that no output meets another tensor
+struct Range {
+    const char* lo;
+    size_t bytes;
+    bool out;
+};
+
+inline bool overlap(const Range& a, const Range& b)
+{
+    return a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes;
+}
+
+// true when an output range meets any other range
+inline bool outputs_overlap(const Range* r, int n)
+{
+    for (int a = 0; a < n; a++)
+        for (int b = a + 1; b < n; b++)
+            if ((r[a].out || r[b].out) && overlap(r[a], r[b])) return true;
+    return false;
+}
 
 }  // namespace mirast

@@ -9,26 +9,6 @@ using namespace mirast;
 
 namespace {
 
-struct Range {
-    const char* lo;
-    size_t bytes;
-    bool out;
-};
-
-bool overlap(const Range& a, const Range& b)
-{
-    return a.bytes && b.bytes && a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes;
-}
-
-// true when an output range meets any other range
-bool outputs_overlap(const Range* r, int n)
-{
-    for (int a = 0; a < n; a++)
-        for (int b = a + 1; b < n; b++)
-            if ((r[a].out || r[b].out) && overlap(r[a], r[b])) return true;
-    return false;
-}
-
 constexpr int DN_MAX_P = (1 << 30) - 1;   // src_of has 2 P int32 entries, and 2 P rows must be an int
 
 struct DensifyLayout {
@@ -171,7 +151,7 @@ int mi_train_densify_plan(int P, const float* xyz_gradient_accum, const float* d
     int* totals = (int*)(ws + l.totals);
     hipLaunchKernelGGL(densify_plan_kernel, dim3(l.nblocks), dim3(TS_THREADS), 0, stream, P, xyz_gradient_accum, denom, scaling, opacity, th, flags,
                        block_counts);
-    hipLaunchKernelGGL(densify_scan_kernel, dim3(1), dim3(TS_THREADS), 0, stream, l.nblocks, (const int*)block_counts, block_offsets, totals);
+    hipLaunchKernelGGL(block_scan_kernel<DC_N>, dim3(1), dim3(TS_THREADS), 0, stream, l.nblocks, (const int*)block_counts, block_offsets, totals);
     hipLaunchKernelGGL(densify_map_kernel, dim3(l.nblocks), dim3(TS_THREADS), 0, stream, P, (const unsigned char*)flags, (const int*)block_offsets,
                        (const int*)totals, (int*)(ws + l.src_of), (int*)(ws + l.rank_of), split_rows);
     HIP_TRY(hipGetLastError());
@@ -215,7 +195,7 @@ int mi_train_densify_apply(int P, const int* counts, int n_tensors, const float*
         if (kinds[k] == DK_ROTATION && cols[k] != 4) return fail(MI_RAST_ERR_INVALID, "densify: rotation has 4 columns");
         at[kinds[k]] = k;
         seen[kinds[k]]++;
-        T.t[k] = {src[k], dst[k], cols[k], kinds[k]};
+        T.t[k] = {src[k], dst[k], cols[k], kinds[k] == DK_MOMENT};
         r[2 * k] = {(const char*)src[k], (size_t)P * cols[k] * sizeof(float), false};
         r[2 * k + 1] = {(const char*)dst[k], (size_t)new_rows * cols[k] * sizeof(float), true};
         if ((size_t)new_rows * cols[k] > longest) longest = (size_t)new_rows * cols[k];
@@ -228,9 +208,7 @@ int mi_train_densify_apply(int P, const int* counts, int n_tensors, const float*
     if (new_rows == 0) return MI_RAST_OK;
     const char* ws = (const char*)workspace;
     const int* src_of = (const int*)(ws + l.src_of);
-    size_t gx = (longest + TS_THREADS - 1) / TS_THREADS;
-    if (gx > 2048) gx = 2048;
-    hipLaunchKernelGGL(densify_gather_kernel, dim3((unsigned)gx, (unsigned)n_tensors), dim3(TS_THREADS), 0, stream, T, P, (int)new_rows, (int)n_orig, src_of);
+    hipLaunchKernelGGL(row_gather_kernel<true>, dim3(gather_grid_x(longest), (unsigned)n_tensors), dim3(TS_THREADS), 0, stream, T, P, (int)new_rows, (int)n_orig, src_of);
     if (n_child > 0)
         hipLaunchKernelGGL(densify_children_kernel, dim3((unsigned)((n_child + TS_THREADS - 1) / TS_THREADS)), dim3(TS_THREADS), 0, stream, P, (int)n_split,
                            (int)n_child, (int)(n_orig + n_clone), src_of, (const int*)(ws + l.rank_of), src[at[DK_XYZ]], src[at[DK_SCALING]],

@@ -8,10 +8,12 @@
 
 #include <stdint.h>
 
+#include "row_compact.h"   // block_rank, the scan of the block counts, the gather: shared with model_edit.h
+
 namespace mirast {
 
-constexpr int TS_THREADS = 256;
-constexpr int TS_WAVES = TS_THREADS / 64;
+constexpr int TS_THREADS = RC_THREADS;
+constexpr int TS_WAVES = RC_WAVES;
 
 // ---- (a) multi-tensor Adam ----------------------------------------------------------------------------------------------------
 // A tensor is cut into tiles of TS_THREADS * ADAM_VEC float4 (4096 floats).  The table carries, per tensor, the first tile's global
@@ -129,7 +131,7 @@ __global__ void __launch_bounds__(TS_THREADS) densify_stats_kernel(int P, const 
 enum : int { DN_CLONE = 1, DN_SPLIT = 2, DN_KEEP_ORIG = 4, DN_KEEP_CLONE = 8, DN_KEEP_CHILD = 16 };
 enum : int { DC_CLONES = 0, DC_SPLITS, DC_KEEP_ORIG, DC_KEEP_CLONE, DC_KEEP_CHILD, DC_N };
 enum : int { DK_COPY = 0, DK_MOMENT = 1, DK_XYZ = 2, DK_SCALING = 3, DK_ROTATION = 4 };
-constexpr int DN_MAX_TENSORS = 32;
+constexpr int DN_MAX_TENSORS = RC_MAX_TENSORS;
 
 struct DensifyThresholds {      // each rounded to binary32 once, as a comparison of a float32 tensor with a Python number is
     float max_grad;
@@ -143,24 +145,6 @@ __device__ __forceinline__ float max3(float a, float b, float c) { return fmaxf(
 // log(exp(s) / (0.8 N)), N = 2, with the division as a multiplication by the binary32 reciprocal: that is how the device evaluates
 // `tensor / 1.6`; a true division can differ in the last bit
 __device__ __forceinline__ float child_log_scale(float s) { return logf(expf(s) * (1.f / 1.6f)); }
-
-// the number of lanes below this one, and in the waves before this one, whose predicate holds; `lds` has TS_WAVES ints
-__device__ __forceinline__ int block_rank(bool pred, int* lds, int& block_total)
-{
-    const unsigned long long mask = __ballot(pred);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();     // the previous use of lds is over
-    if (lane == 0) lds[wave] = __popcll(mask);
-    __syncthreads();
-    int before = __popcll(mask & ((1ull << lane) - 1ull)), total = 0;
-    for (int w = 0; w < TS_WAVES; w++) {
-        const int c = lds[w];
-        if (w < wave) before += c;
-        total += c;
-    }
-    block_total = total;
-    return before;
-}
 
 // One thread per row: the row's class and what survives the final prune (scene/gaussian_model.py:566-578, N = 2), and the
 // workgroup's count of each.  The reference zeroes max_radii2D in densification_postfix before it evaluates
@@ -196,34 +180,6 @@ __global__ void __launch_bounds__(TS_THREADS) densify_plan_kernel(int P, const f
     }
 }
 
-// One workgroup: exclusive scan of the per-workgroup counts, class by class, and the totals.
-__global__ void __launch_bounds__(TS_THREADS) densify_scan_kernel(int nblocks, const int* __restrict__ block_counts, int* block_offsets, int* totals)
-{
-    __shared__ int part[TS_THREADS];
-    const int tid = threadIdx.x;
-    const int per = (nblocks + TS_THREADS - 1) / TS_THREADS;
-    const int b0 = min(tid * per, nblocks), b1 = min(b0 + per, nblocks);
-    for (int k = 0; k < DC_N; k++) {
-        int sum = 0;
-        for (int b = b0; b < b1; b++) sum += block_counts[b * DC_N + k];
-        __syncthreads();
-        part[tid] = sum;
-        __syncthreads();
-        for (int d = 1; d < TS_THREADS; d <<= 1) {
-            const int add = tid >= d ? part[tid - d] : 0;
-            __syncthreads();
-            part[tid] += add;
-            __syncthreads();
-        }
-        int run = part[tid] - sum;
-        for (int b = b0; b < b1; b++) {
-            block_offsets[b * DC_N + k] = run;
-            run += block_counts[b * DC_N + k];
-        }
-        if (tid == TS_THREADS - 1) totals[k] = part[tid];
-    }
-}
-
 // One thread per row: where the row, its clone and its children go.  Output rows: kept originals, kept clones, kept first children,
 // kept second children; src_of[output row] = input row.  rank_of[kept child pair] and split_rows[split] tell which normal samples
 // belong to a split row (the samples are drawn for every split row, also those whose children the prune deletes).
@@ -250,34 +206,9 @@ __global__ void __launch_bounds__(TS_THREADS) densify_map_kernel(int P, const un
     }
 }
 
-struct GatherEntry {
-    const float* src;
-    float* dst;
-    int cols;
-    int kind;
-};
-
-struct GatherTable {
-    GatherEntry t[DN_MAX_TENSORS];
-};
-
-// blockIdx.y = tensor; grid-stride over its new_rows * cols elements.  Parameters: every output row is its source row, bit for bit
-// (a child's xyz and scaling are overwritten by densify_children_kernel).  Moments: kept originals copy theirs, every new row is 0.
-__global__ void __launch_bounds__(TS_THREADS) densify_gather_kernel(const GatherTable T, int P, int new_rows, int n_orig, const int* __restrict__ src_of)
-{
-    const GatherEntry e = T.t[blockIdx.y];
-    const size_t total = (size_t)new_rows * e.cols;
-    for (size_t x = (size_t)blockIdx.x * TS_THREADS + threadIdx.x; x < total; x += (size_t)gridDim.x * TS_THREADS) {
-        const int j = (int)(x / e.cols), c = (int)(x - (size_t)j * e.cols);
-        float val = 0.f;
-        if (e.kind != DK_MOMENT || j < n_orig) {
-            int s = src_of[j];
-            if ((unsigned)s >= (unsigned)P) s = 0;     // counts that are not the plan's cannot make this read leave the tensor
-            val = e.src[(size_t)s * e.cols + c];
-        }
-        e.dst[x] = val;
-    }
-}
+// The gather itself is row_gather_kernel<true> of row_compact.h.  Parameters: every output row is its source row, bit for bit (a
+// child's xyz and scaling are overwritten by densify_children_kernel).  Moments (zero_new): kept originals copy theirs, every new
+// row is 0.
 
 // One thread per kept pair of children: xyz = R(q / |q|) sample + xyz_parent (utils/general_utils.py:78-99, the bmm's order of
 // summation), scaling = log(exp(s) / 1.6).
