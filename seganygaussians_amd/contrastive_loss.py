@@ -74,7 +74,7 @@ def draw_sampled_scales(sorted_scales: torch.Tensor, sampled_scale_index: torch.
 @dataclass
 class ContrastiveTargets:
     """What sample_contrastive_targets hands to the front end and to contrastive_loss.  Public: sampled_ray (H, W) bool,
-    ray_yx (S, 2) int32 (row-major), sampled_scales (N,) f32 before q_trans, scale_index (N,) and upper_bound (N,) on the host.
+    ray_yx (S, 2) int32 (row-major), sampled_scales (N,) f32 before q_trans (scale_gate.scale_gates takes them as they are), scale_index (N,) and upper_bound (N,) on the host.
     The rest is device state of the loss kernels (include/mi_contrastive.h)."""
     sampled_ray: torch.Tensor
     ray_yx: torch.Tensor
@@ -102,7 +102,7 @@ class ContrastiveTargets:
 
 def sample_contrastive_targets(masks, mask_scales: torch.Tensor, upper_bound_scale: float, num_sampled_rays: int = 1000,
                                ray_sample_rate: float = 0, num_sampled_scales: int = 8, device=None) -> ContrastiveTargets:
-    """train_contrastive_feature.py:145-226 without :228 (q_trans is the caller's): the sampled rays, the sampled scales and the
+    """train_contrastive_feature.py:145-226 without :228 (q_trans is scale_gate.py's, fused with the gates): the sampled rays, the sampled scales and the
     per-ray, per-scale gt bitsets.  `masks` is a PackedSamMasks or bool (M, H, W) masks (packed here, on the device);
     `mask_scales` (M,) float32 in the masks' order.  Draws the reference's CPU random numbers in its order."""
     if isinstance(masks, PackedSamMasks):

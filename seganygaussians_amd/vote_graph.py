@@ -9,7 +9,8 @@ Segmentation" between the feature render and the Jaccard clustering, and from th
   * cluster_scores(), cluster_queries() -- plain torch over a few thousand numbers: the mean score per cluster and the notebook's
                            choice of query features and scales.
 
-The CLIP and SAM networks, the tokenizer and the QuantileTransformer stay with the caller: `gates` is scale_gate(q_trans(scales)).
+The CLIP and SAM networks and the tokenizer stay with the caller; `gates` is scale_gate(q_trans(scales)), which
+scale_gate.scale_gates(scales, sq, weight, bias) gives in one launch.
 No autograd: inputs that require grad are refused while grad mode is on.  There is no CPU fallback for the device parts."""
 from __future__ import annotations
 
@@ -39,8 +40,8 @@ def sam_mask_features(rendered: torch.Tensor, masks, gates: torch.Tensor, size=N
     """The notebook's per-view mask descriptors.
 
     rendered: float32 (C, H, W) on a GPU, as render_contrastive_feature(..., norm_point_features=True) returns it, 1 <= C <= 256.
-    masks: bool (M, hm, wm) on the CPU or that GPU, or a PackedSamMasks on it.  gates: float32 (M, C), scale_gate(q_trans(scales)).
-    size: the working resolution (h, w), default (H // 4, W // 4).  With f_p the bilinear sample (align_corners=False) of rendered
+    masks: bool (M, hm, wm) on the CPU or that GPU, or a PackedSamMasks on it.  gates: float32 (M, C), scale_gate(q_trans(scales))
+    (scale_gate.scale_gates).  size: the working resolution (h, w), default (H // 4, W // 4).  With f_p the bilinear sample (align_corners=False) of rendered
     at working pixel p and b_m the masks resampled to (h, w) and eroded (erode_sam_masks(masks, size, min_sum)):
 
         s_m = sum_{p in b_m} (g_m * f_p) / max(|g_m * f_p|, 1e-12) / (n_m + 1e-9),      row m = s_m / max(|s_m|, 1e-12)
