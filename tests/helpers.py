@@ -217,6 +217,9 @@ class GpuRun:
         dbits = self.geom_fields()["depths"].view(np.uint32)[pl].astype(np.uint64)
         return (tiles << np.uint64(32)) | dbits
 
+    def run_bounds(self):
+        return run_bounds(self.img, self.inp.image_width, self.inp.image_height)
+
     def img_fields(self):
         from seganygaussians_amd import _lib
         i = self.inp
@@ -228,6 +231,28 @@ class GpuRun:
                     ranges=self._view(self.img, off["ranges"], 2 * tiles, np.uint32),
                     tile_consumed=self._view(self.img, off["tile_consumed"], tiles, np.uint32),
                     tile_nsurv=self._view(self.img, off["tile_nsurv"], tiles, np.uint32))
+
+
+def run_words(img, W, H):
+    """The 16 words at MI_IMG_NUM_RENDERED + 8192 bytes of a forward's image buffer (include/mi_rast.h, mi_rast_forward_reuse's
+    cached_words): {list entries, longest list, -, key bits, then the nine XCD run boundaries of the blend kernels}."""
+    from seganygaussians_amd import _lib
+    _, off = _lib.image_layout(W, H)
+    o = off["num_rendered"] + 8192
+    return img.detach().cpu().numpy()[o:o + 64].view(np.uint32).copy()
+
+
+def run_bounds(img, W, H):
+    """The nine boundaries of the eight XCD runs (csrc/xcd_runs.h) that the range scan of the forward published."""
+    return run_words(img, W, H)[4:13].astype(np.int64)
+
+
+def tile_ranges(img, W, H):
+    """(tiles, 2) ranges of the tile lists in a forward's image buffer."""
+    from seganygaussians_amd import _lib
+    _, off = _lib.image_layout(W, H)
+    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    return img.detach().cpu().numpy()[off["ranges"]:off["ranges"] + 8 * tiles].view(np.uint32).reshape(-1, 2).astype(np.int64)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -9,9 +9,9 @@ reference_quirks=True on the float32 input values:
     bound = max(FACTOR * E32, FLOOR * magnitude of the terms summed into the group)
     every non-excused group:  |product - dense64| <= bound;  a group dense64 leaves at exactly zero is exactly zero, and the reverse.
 
-Magnitude of the terms of a gradient row: the loss is split by 4 x 4 pixel blocks, each block's float64 gradient is taken on its
-own and the absolute values are added (a lower bound of the true sum of term magnitudes: the floor can only be too strict).  Of a
-pixel: sum_g w_g |c_g| + T |bg| from the dense weights.
+Magnitude of the terms of a gradient row: the loss is split by 4 x 4 pixel blocks (8 x 8 on the many-tile scenes), each block's
+float64 gradient is taken on its own and the absolute values are added (a lower bound of the true sum of term magnitudes: the
+floor can only be too strict).  Of a pixel: sum_g w_g |c_g| + T |bg| from the dense weights.
 
 The fp64 reference and a float32 kernel must take the same discrete decisions; a pixel in which a pair sits within a MARGIN of a
 decision is excused, with every Gaussian blended there.  The designed classes are never excused and at most EXCUSED_GAUSSIANS /
@@ -46,6 +46,8 @@ CHK = _constant("blend_bwd_shared.h", "CHK")   # rows per MFMA chunk of the back
 FB = _constant("blend_fwd.h", "FB")            # blend-list records per forward batch
 XB = _constant("blend_fwd_x3.h", "XB")         # blend-list records per batch of the tile-batched forward
 ROWS = _constant("blend_bwd.h", "ROWS")        # survivor rows resident in LDS at a time in the backward
+RUN_CAP = _constant("mi_rast.hip", "RUN_MODEL_CAP")   # range scan: XCD runs of equal sum(min(list length, RUN_CAP) + RUN_FIX)
+RUN_FIX = _constant("mi_rast.hip", "RUN_MODEL_FIX")
 LIST_LENGTHS = tuple(sorted({n + d for n in (XG, CHK, 64, FB, XB, ROWS) for d in (-1, 0, 1)}))
 
 EXCUSED_GAUSSIANS = 2
@@ -77,15 +79,37 @@ MUTUAL = {
     "dL_drotations": (256.0, -22, 0.656),
 }
 
+# The same procedure (calibrate(), unchanged) run over tile_cases() alone: the many-tile scenes "tiles" below (97 x 33 and 177 x 17)
+# have lists of 200 and more entries in one tile of many, a Gaussian summed from every tile, walks that end early and centres at
+# x = 90 to 170, and the two float32 restatements differ by more there than MUTUAL allows (judged against each other with MUTUAL
+# they reach 2 to 12 times the bound for final_T and the image).  Worst mutual error / bound under MUTUAL_TILES: 0.986.
+# MUTUAL and all_cases() stay as they are; rule() picks the table by the case's scene kind.
+MUTUAL_TILES = {
+    # class: (FACTOR, log2 FLOOR, worst mutual error / bound)
+    "image": (64.0, -21, 0.955),
+    "final_T": (4.0, -19, 0.866),
+    "out_mask": (16.0, -19, 0.974),
+    "out_depth": (4.0, -19, 0.82),
+    "dL_dcolors": (128.0, -22, 0.686),
+    "dL_dsh": (64.0, -22, 0.744),
+    "dL_dmask": (128.0, -22, 0.831),
+    "dL_dmeans2D": (256.0, -22, 0.676),
+    "dL_dopacity": (16.0, -15, 0.674),
+    "dL_dmeans3D": (128.0, -17, 0.986),
+    "dL_dscales": (128.0, -22, 0.812),
+    "dL_drotations": (128.0, -18, 0.764),
+}
+TABLES = {"edge": MUTUAL, "list": MUTUAL, "tiles": MUTUAL_TILES}
 
-def rule(cls):
-    """(FACTOR, FLOOR) the product is judged with."""
-    f, lf, _ = MUTUAL[cls]
+
+def rule(cls, scene="edge"):
+    """(FACTOR, FLOOR) the product is judged with, on a case of scene kind `scene`."""
+    f, lf, _ = TABLES[scene][cls]
     return 2.0 * f, 2.0 ** lf
 
 
-def mutual_rule(cls):
-    f, lf, _ = MUTUAL[cls]
+def mutual_rule(cls, scene="edge"):
+    f, lf, _ = TABLES[scene][cls]
     return f, 2.0 ** lf
 
 
@@ -93,8 +117,9 @@ def mutual_rule(cls):
 
 Variant = namedtuple("Variant", "colors mask mask_only cov modifier bg P kind L", defaults=("precomp", False, False, False, 1.0,
                                                                                             "zero", 96, None, None))
-# colors: "precomp" | "sh0" | "sh3";  kind / L: the list-length scene ("contrib" | "raw", length);  P: total number of Gaussians
-# (designed + make_scene fill) of the edge scene, or "culled" for the scene in which every Gaussian is behind the near plane.
+# colors: "precomp" | "sh0" | "sh3";  kind / L: the list-length scene ("contrib" | "raw", length), or kind "t1" | "t2" of the
+# many-tile scenes;  P: total number of Gaussians (designed + make_scene fill) of the edge and many-tile scenes, or "culled" for
+# the scene in which every Gaussian is behind the near plane.
 
 NEAR = np.float32(0.2)
 
@@ -261,10 +286,108 @@ def list_scene(W, H, C, seed, variant: Variant):
                    np.array([r[2] for r in rows]) / variant.modifier, [r[3] for r in rows], [r[4] for r in rows])
 
 
+# ---- scenes of many tiles and uneven density -------------------------------------------------------------------------------------
+# What only exists with many tiles: a gradient row summed by atomics from every tile, the eight XCD runs cut at equal modelled
+# work (csrc/tile_ranges.h, xcd_runs.h) with their queued halves, empty ranges between occupied tiles, a last tile column / row
+# one pixel wide, a tile whose walk ends long before its list.  Two images whose partial last tiles buy many tiles for few pixels
+# (the dense float64 reference is O(P W H)):
+#   "t1"  97 x 33: 7 x 3 tiles, last tile column and last tile row 1 px wide;   "t2"  177 x 17: 12 x 2 tiles, last row 1 px tall.
+TILE_SIZES = {"t1": (97, 33), "t2": (177, 17)}
+DENSE_LIST = max(LIST_LENGTHS) + 1       # raw entries the dense tile's list holds at least
+DENSE_TILE = {"t1": (5, 1), "t2": (10, 0)}   # (tile column, tile row)
+OPAQUE_TILE = (0, 1)                     # t1
+EMPTY_BAND = (4, 5, 6)                   # t2: tile columns of the top tile row
+N_DENSE = {"t1": 200, "t2": 240}         # Gaussians inside the dense tile: long enough a list for an XCD run of one tile
+
+
+def _tiles_designed(which, W, H, focal, seed):
+    b = _Builder(W, H, focal, np.random.default_rng(seed + 9000))
+
+    def quat():
+        return tuple(_unit(b.rng.normal(0, 1, 4)))
+
+    def inside(cls, tile, n, op):
+        # rects that stay inside the one tile: a largest sigma of 1.5 px is radius 6 at most (the low-pass and the perspective
+        # factor included), centres 6.2 to 10.6 px into the tile; anisotropic and rotated, so that every gradient class has terms.
+        # (Sigmas of 0.5 to 0.8 px were tried first: at x = 90 or 170 the float32 rounding of the centre alone moves such a row
+        # of dL_dopacity by 2^-15 of its terms, and the class would have needed FACTOR 512.)
+        for _ in range(n):
+            b.add(cls, 16 * tile[0] + b.rng.uniform(6.4, 10.4), 16 * tile[1] + b.rng.uniform(6.4, 10.4),
+                  sig=(1.5, b.rng.uniform(1.2, 1.5), b.rng.uniform(1.2, 1.5)), q=quat(), op=b.rng.uniform(*op))
+
+    if which == "t1":
+        # in front of everything, in every tile, blended at every pixel (0.1 exp(-r^2 / (2 * 26^2)) stays above 1/255 out to 66 px)
+        b.add("spanning_front", b.cx + 0.3, b.cy + 0.2, z=0.6, sig=(30.0, 26.0, 28.0), q=quat(), op=0.1)
+        # seven near-opaque Gaussians over tile (0, 1) end every pixel's walk there: alpha >= 0.78 on the tile, 0.9 * 0.22^7 < 1e-4;
+        # sigma 16 is radius 53: tile columns 0 to 3, short of the dense tile's neighbours.  0.98 stays below the 0.99 clamp, whose
+        # contour would cross the tile otherwise
+        ou, ov = 16 * OPAQUE_TILE[0] + 8, 16 * OPAQUE_TILE[1] + 8
+        for i in range(7):
+            b.add("opaque_front", ou, ov, z=0.8 + 0.01 * i, sig=16.0, op=0.98)
+        inside("hidden", OPAQUE_TILE, 30, (0.3, 0.8))
+        for k in range(1, 7):                 # every interior tile corner of the middle tile row: four tiles each
+            for y in (16, 32):                # (the two on the opaque tile's corners in front of it: they blend there as well)
+                b.add("corner", 16 * k, y, sig=1.5, z=(0.7 + y / 3200) if k == 1 else None)
+        # centres off the image: alpha >= 1/255 on x = 96 (y = 32) alone -- one pixel further in it is at most 0.6 / 255
+        for y in (7.3, 22.6, 31.4):
+            b.add("last_column", W + 1.3, y, sig=0.8, op=0.15)
+        for x in (40.3, 56.4, 88.3):
+            b.add("last_row", x, H + 1.3, sig=0.8, op=0.3)
+        inside("dense_tile", DENSE_TILE[which], N_DENSE[which], (0.01, 0.08))
+        b.add("spanning_back", b.cx - 0.3, b.cy - 0.2, z=b.depth() + 5.0, sig=(26.0, 30.0, 28.0), q=quat(), op=0.1)
+    else:
+        for x in (32, 48, 128, 144):          # the tile corners on either side of the empty band, one tile away from it
+            b.add("corner", x, 16, sig=1.5)
+        inside("dense_tile", DENSE_TILE[which], N_DENSE[which], (0.01, 0.08))
+    return b.rows
+
+
+def tiles_scene(W, H, C, seed, variant: Variant):
+    """variant.kind "t1" / "t2": the designed classes above, then a make_scene fill of variant.P - (designed) Gaussians -- of which
+    t2 drops those that could reach its empty band (the band is a designed property, the fill is not)."""
+    which = variant.kind
+    assert (W, H) == TILE_SIZES[which]
+    cam, focal = _camera(W, H)
+    rows = _tiles_designed(which, W, H, focal, seed)
+    n_fill = max(0, variant.P - len(rows))
+    fill = scenes.make_scene(n_fill, W, H, focal, C, math.log(0.12 * 33.3 / focal), 0.5, seed=seed, z_range=(1.0, 6.0))
+    keep = np.ones(n_fill, bool)
+    if which == "t2":
+        m = fill.means3D.astype(np.float64)
+        u = focal * m[:, 0] / m[:, 2] + (W - 1) * 0.5
+        # 3 sigma of the largest axis with the perspective factor (at most 1 + tan^2) and the low-pass, and 2 px on top
+        r = 3.0 * np.sqrt(1.5 * (fill.scales.astype(np.float64).max(axis=1) * focal / m[:, 2]) ** 2 + 0.3) + 2.0
+        keep = (u + r < 16 * EMPTY_BAND[0]) | (u - r >= 16 * (EMPTY_BAND[-1] + 1))
+    classes = [r[0] for r in rows] + ["fill"] * int(keep.sum())
+    cat = lambda i, a, n: np.concatenate([np.array([r[i] for r in rows], np.float64).reshape(-1, n), a.astype(np.float64)[keep]])
+    scl = cat(2, fill.scales, 3)
+    if variant.modifier != 1.0:
+        scl = scl / variant.modifier
+    return _finish(W, H, C, seed, variant, cam, classes, cat(1, fill.means3D, 3), scl, cat(3, fill.rotations, 4),
+                   cat(4, fill.opacities, 1))
+
+
+def tile_lists(ref):
+    """(tile rows, tile columns) list lengths of a case from the oracle's full-list ranges."""
+    inp = ref.inp
+    gx, gy = (inp.image_width + 15) // 16, (inp.image_height + 15) // 16
+    r = np.asarray(ref.fwd.state.field(so.F_RANGES), np.int64).reshape(gy * gx, 2)
+    return (r[:, 1] - r[:, 0]).reshape(gy, gx)
+
+
+def model_runs(ref):
+    """The nine XCD run boundaries tile_ranges_kernel publishes by default for the case (csrc/tile_ranges.h: equal sums of
+    min(list length, RUN_CAP) + RUN_FIX over the row-major tiles, restated by tests/test_xcd_mapping.py) on the oracle's full
+    lists, and those of equal tile counts."""
+    from tests.test_xcd_mapping import bounds_from_model, run_start
+    lists = tile_lists(ref).reshape(-1)
+    return bounds_from_model(lists, RUN_CAP, RUN_FIX), [run_start(x, len(lists)) for x in range(9)]
+
+
 def make_inputs(case):
     """case = (scene function name, W, H, C, seed, Variant)."""
     fn, W, H, C, seed, v = case
-    return {"edge": edge_scene, "list": list_scene}[fn](W, H, C, seed, v)
+    return {"edge": edge_scene, "list": list_scene, "tiles": tiles_scene}[fn](W, H, C, seed, v)
 
 
 def gradient_images(inp, seed):
@@ -307,7 +430,7 @@ def classes_of_grads(inp, g):
     return out
 
 
-def _dense(inp, dL, dLm, dt, quirks, magnitudes):
+def _dense(inp, dL, dLm, dt, quirks, magnitudes, block=4):
     W, H, C = inp.image_width, inp.image_height, inp.channels
     P = np.asarray(inp.means3D).reshape(-1, 3).shape[0]
     t = lambda a, g=True: None if a is None else torch.tensor(np.asarray(a, np.float64), dtype=dt, requires_grad=g)
@@ -327,9 +450,10 @@ def _dense(inp, dL, dLm, dt, quirks, magnitudes):
     total = [torch.zeros_like(x) for x in leaves]
     mags = [torch.zeros_like(x) for x in leaves]
     if magnitudes:
-        # one batched backward over the 4 x 4 pixel blocks: block b's loss is the sum of `prod` over its pixels
-        by, bx = (H + 3) // 4, (W + 3) // 4
-        ys, xs = torch.meshgrid(torch.arange(H) // 4, torch.arange(W) // 4, indexing="ij")
+        # one batched backward over the block x block pixel blocks (4 x 4; coarser for the many-tile scenes, which only lowers
+        # the floor): block b's loss is the sum of `prod` over its pixels
+        by, bx = (H + block - 1) // block, (W + block - 1) // block
+        ys, xs = torch.meshgrid(torch.arange(H) // block, torch.arange(W) // block, indexing="ij")
         sel = torch.nn.functional.one_hot((ys * bx + xs).reshape(-1), by * bx).T.reshape(by * bx, 1, H, W).to(dt)
         gs = torch.autograd.grad(prod, leaves, grad_outputs=sel.expand(-1, C, -1, -1), retain_graph=True, allow_unused=True,
                                  is_grads_batched=True)
@@ -402,6 +526,7 @@ def oracle_classes(inp, dL, dLm):
 
 
 MASK_ONLY_CLASSES = ("out_mask", "dL_dmask")
+MAG_BLOCK = {"tiles": 8}     # pixel-block edge of the term magnitudes per scene kind (4 unless named): a 290-Gaussian case stays affordable
 
 
 class Reference:
@@ -418,7 +543,7 @@ class Reference:
         threads = torch.get_num_threads()
         try:
             torch.set_num_threads(min(4, threads))
-            self.d64, self.mag, ref = _dense(inp, self.dL, self.dLm, torch.float64, quirks, True)
+            self.d64, self.mag, ref = _dense(inp, self.dL, self.dLm, torch.float64, quirks, True, MAG_BLOCK.get(case[0], 4))
             torch.set_num_threads(1)
             self.d32, _, ref32 = _dense(inp, self.dL, self.dLm, torch.float32, quirks, False)
         finally:
@@ -498,7 +623,7 @@ class Reference:
         assert classes is not None or set(self.classes) <= set(product), sorted(set(self.classes) - set(product))
         for cls in (classes or self.classes):
             assert cls in product, (name, cls, "missing from the product's outputs")
-            f, fl = rule(cls)
+            f, fl = rule(cls, self.case[0])
             r, zd = self.ratios(cls, product[cls], f, fl, extra=None if extra is None else extra.get(cls))
             worst[cls] = float("nan") if np.isnan(r).any() else float(r.max()) if r.size else 0.0
             bad = np.flatnonzero(~(r <= 1.0) | zd)
@@ -562,6 +687,10 @@ SMALL_CONFIGS = ("rgb",) + FEATURE_CONFIGS     # the small sizes and P = 1: RGB,
 SEEDS = {
     ("list", 16, 16, "sh3", "raw", 128): 4,      # seed 3: one colour channel within 6e-6 of the clamp at 0
     ("edge", 16, 16, "precomp", None, None): 4,  # seed 3: a fill Gaussian within 1e-5 of alpha = 1/255 on pixel (14, 14)
+    # seeds 2, 4 and 5: a pair on a decision in one pixel of the dense tile, which excuses every Gaussian blended there (150 and
+    # more); seed 3 is clean and cuts the runs without one of a single tile; seed 6 is clean and leaves the dense tile a run of its own
+    ("tiles", 97, 33, "precomp", "t1", None): 6,
+    ("tiles", 97, 33, "sh3", "t1", None): 6,
 }
 
 
@@ -590,8 +719,24 @@ def list_cases(cfg):
     return [list_case(cfg, kind, L) for kind in ("contrib", "raw") for L in LIST_LENGTHS]
 
 
+TILE_CONFIGS = {"t1": ("rgb", "mask_depth", "mask_only", "c32", "c64"), "t2": ("c32", "rgb")}
+TILE_P = {"t1": 266, "t2": 290}      # designed + fill
+
+
+def tile_case(which, cfg):
+    C, v = CONFIGS[cfg]
+    W, H = TILE_SIZES[which]
+    v = v._replace(P=TILE_P[which], kind=which)
+    return ("tiles", W, H, C, _seed("tiles", W, H, v), v)
+
+
+def tile_cases():
+    """The many-tile scenes in their configurations: a calibration input of their own (MUTUAL_TILES), not part of all_cases()."""
+    return [tile_case(which, cfg) for which, cfgs in TILE_CONFIGS.items() for cfg in cfgs]
+
+
 def all_cases():
-    """Every case a GPU test uses."""
+    """Every case a GPU test of the edge and list scenes uses (the input of MUTUAL's calibration)."""
     out = []
     for cfg in CONFIGS:
         out.append(edge_case(cfg))
@@ -643,7 +788,15 @@ def calibrate(cases, floor_first=True):
 
 
 if __name__ == "__main__":
-    for first in (True, False):
-        print("FLOOR lowered first (the committed table):" if first else "FACTOR lowered first (for comparison, DESIGN.md 2a):")
-        for k, v in sorted(calibrate(all_cases(), floor_first=first).items()):
+    import sys
+    which = sys.argv[1:] or ["edge", "tiles"]      # `python -m tests.raster_edge_ref tiles`: the second table alone
+    if "edge" in which:
+        for first in (True, False):
+            print("MUTUAL, FLOOR lowered first (the committed table):" if first else
+                  "MUTUAL, FACTOR lowered first (for comparison, DESIGN.md 2a):")
+            for k, v in sorted(calibrate(all_cases(), floor_first=first).items()):
+                print(f'    "{k}": {v},')
+    if "tiles" in which:
+        print("MUTUAL_TILES, FLOOR lowered first (the committed table):")
+        for k, v in sorted(calibrate(tile_cases()).items()):
             print(f'    "{k}": {v},')

@@ -100,6 +100,15 @@ def test_small_sizes_one_gaussian_and_all_culled(cfg, full_lists):
         _lift_case(case, full_lists, worst)
 
 
+@FULL
+@pytest.mark.parametrize("tile", [("t1", "c64"), ("t2", "c32")], ids=["t1-c64", "t2-c32"])
+def test_many_tile_scenes_against_dense64(tile, full_lists):
+    """The 97 x 33 and 177 x 17 scenes of er.tile_cases() (21 and 24 tiles: a vote row summed from every tile, XCD runs of uneven
+    length, empty ranges between occupied tiles, one-pixel tile columns and rows) under their table, er.MUTUAL_TILES."""
+    worst = {}
+    _lift_case(er.tile_case(*tile), full_lists, worst)
+
+
 def test_reuse_reads_the_buffers_of_any_forward():
     """Lifts over the state of an earlier lift, of a feature forward and of a mask-only forward of the same view: each under the rule
     of the first test, and none of them changes a byte of the three buffers."""

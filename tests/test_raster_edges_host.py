@@ -1,7 +1,8 @@
 """CPU half of the rasterizer's edge tests (tests/raster_edge_ref.py; the GPU half is tests/test_raster_edges.py): for every scene
 and variant the GPU tests use -- the caps on excused groups, radii equal to the oracle's, the mutual calibration check of FACTOR and
 FLOOR, the oracle against dense float64 per group under the final rule, the exact-zero groups, and that each designed class is
-what its name says.  It also closes a hole in the oracle's own pin (tests/test_oracle_dense.py never had a Gaussian beyond the
+what its name says; the same for the many-tile scenes of er.tile_cases() under their own table (MUTUAL_TILES), with the
+properties those scenes are designed for and the XCD runs they give.  It also closes a hole in the oracle's own pin (tests/test_oracle_dense.py never had a Gaussian beyond the
 1.3 tan(fov) clamp or a saturated alpha): with dense_ref's reference_quirks the oracle agrees with autograd there per row."""
 import numpy as np
 import pytest
@@ -10,13 +11,14 @@ from oracle import saga_oracle as so
 from tests import raster_edge_ref as er
 
 CASES = er.all_cases()
+TILE_CASES = er.tile_cases()
 
 
 def _id(case):
     fn, W, H, C, seed, v = case
     tags = [fn, f"{W}x{H}", f"C{C}", v.colors] + [k for k in ("mask", "mask_only", "cov") if getattr(v, k)]
     tags += [f"mod{v.modifier}"] * (v.modifier != 1.0) + [f"bg-{v.bg}"] * (v.bg != "zero")
-    tags += [f"{v.kind}{v.L}"] * (v.kind is not None) + [f"P{v.P}"] * (v.P != 96)
+    tags += [f"{v.kind}{v.L or ''}"] * (v.kind is not None) + [f"P{v.P}"] * (v.P != 96)
     return "-".join(tags)
 
 
@@ -31,6 +33,12 @@ def _blended(ref):
     return (w > 0).any(axis=1), w > 0
 
 
+def _member_tiles(ref, i, tile_of_pixel):
+    """The tiles whose list holds Gaussian i (input order)."""
+    k = ref.dense["order"].tolist().index(i)
+    return set(tile_of_pixel[ref.dense["member"][k]].tolist())
+
+
 def _evaluated(ref):
     """(P, N) in input order: the pair is in the pixel's tile list and the pixel had not stopped before it."""
     d = ref.dense
@@ -41,7 +49,7 @@ def _evaluated(ref):
     return out
 
 
-@pytest.mark.parametrize("case", CASES, ids=_id)
+@pytest.mark.parametrize("case", CASES + TILE_CASES, ids=_id)
 def test_caps_radii_calibration_and_oracle(case):
     ref = er.reference(case)
     P = len(ref.radii)
@@ -53,7 +61,7 @@ def test_caps_radii_calibration_and_oracle(case):
     np.testing.assert_array_equal(ref.radii32, ref.radii, err_msg="radii: dense32 vs dense64")
     np.testing.assert_array_equal(ref.fwd.state.field(so.F_TILES_TOUCHED)[:P], ref.tiles_touched, err_msg="tile rects")
     for cls in ref.classes:
-        f, fl = er.mutual_rule(cls)
+        f, fl = er.mutual_rule(cls, case[0])
         # the two float32 restatements judge each other with the undoubled constants
         r_o, _ = ref.ratios(cls, ref.oracle[cls], f, fl, e32_from=("d32",))
         r_d, _ = ref.ratios(cls, ref.d32[cls], f, fl, e32_from=("oracle",))
@@ -62,7 +70,7 @@ def test_caps_radii_calibration_and_oracle(case):
     # the oracle under the rule the product is held to, exact zeros included; dense32 takes the same zero decisions
     ref.check("oracle", ref.oracle)
     for cls in ref.classes:
-        _, zd = ref.ratios(cls, ref.d32[cls], *er.rule(cls))
+        _, zd = ref.ratios(cls, ref.d32[cls], *er.rule(cls, case[0]))
         assert not zd.any(), (cls, "dense32 zero groups")
 
 
@@ -157,3 +165,96 @@ def test_small_scenes():
         assert (culled.radii == 0).all() and culled.fwd.num_rendered == 0 and len(culled.radii) > 1
         for W, H in er.SMALL_SIZES:
             assert _blended(er.reference(er.edge_case(cfg, W, H)))[0].any()
+
+
+@pytest.mark.parametrize("case", TILE_CASES, ids=_id)
+def test_tile_scenes_are_what_their_names_say(case):
+    ref = er.reference(case)
+    which, inp, d = case[5].kind, ref.inp, ref.dense
+    W, H = inp.image_width, inp.image_height
+    lists = er.tile_lists(ref)
+    gy, gx = lists.shape
+    blended, where = _blended(ref)
+    tile_of_pixel = (np.arange(H)[:, None] // 16 * gx + np.arange(W)[None] // 16).reshape(-1)
+    tiles_blended = lambda i: set(tile_of_pixel[where[i]].tolist())
+    grad_classes = [c for c in ref.classes if c not in er.PIXEL_CLASSES]
+    # (dL_drotations of an isotropic Gaussian is zero up to rounding: left out for the classes built isotropic)
+    nonzero_row = lambda i, but=(): all(np.abs(ref.d64[c][i]).max() > 0 for c in grad_classes if c not in but)
+    zero_row = lambda i: all(np.abs(ref.d64[c][i]).max() == 0 and np.abs(ref.oracle[c][i]).max() == 0 for c in grad_classes)
+    # the dense tile: a raw list beyond every batch size, next to lists shorter than one backward chunk
+    tx, ty = er.DENSE_TILE[which]
+    assert len(_rows(ref, "dense_tile")) == er.N_DENSE[which] and lists[ty, tx] >= max(er.DENSE_LIST, er.N_DENSE[which])
+    assert all(blended[i] and tiles_blended(i) == {ty * gx + tx} for i in _rows(ref, "dense_tile"))
+    for ny in range(max(0, ty - 1), min(gy, ty + 2)):
+        for nx in range(max(0, tx - 1), min(gx, tx + 2)):
+            assert (nx, ny) == (tx, ty) or lists[ny, nx] < er.CHK, (nx, ny, int(lists[ny, nx]))
+    # corners: blended in four tiles each
+    assert len(_rows(ref, "corner")) == (12 if which == "t1" else 4)
+    for i in _rows(ref, "corner"):
+        assert len(tiles_blended(i)) == 4, (i, tiles_blended(i))
+    if which == "t1":
+        assert (gx, gy) == (7, 3) and W - 16 * (gx - 1) == 1 and H - 16 * (gy - 1) == 1
+        # spanning: one rect over every tile, blended in every tile, first and last of every list
+        front, back = _rows(ref, "spanning_front")[0], _rows(ref, "spanning_back")[0]
+        for i in (front, back):
+            assert ref.tiles_touched[i] == gx * gy and np.asarray(inp.opacities).reshape(-1)[i] <= np.float32(0.1) and nonzero_row(i)
+        # (the rear one not in the opaque tile, nor in the strip of one pixel row under it, which the opaque Gaussians end as well)
+        assert len(tiles_blended(front)) == gx * gy and len(tiles_blended(back)) >= gx * gy - 2
+        vis = [i for i in d["order"].tolist() if ref.radii[i] > 0]
+        assert vis[0] == front and vis[-1] == back
+        # the opaque tile: every pixel's walk ends on the Gaussians at the front, within a quarter of the list
+        ox, oy = er.OPAQUE_TILE
+        in_tile = tile_of_pixel == oy * gx + ox
+        assert not d["alive"][-1][in_tile].any(), "a pixel of the opaque tile that never stops"
+        pos = {g: k for k, g in enumerate(i for i in d["order"].tolist() if (oy * gx + ox) in _member_tiles(ref, i, tile_of_pixel))}
+        assert len(pos) == lists[oy, ox]
+        last = max(pos[i] + 1 for i in range(len(blended)) if where[i][in_tile].any())
+        assert 4 * last <= lists[oy, ox], (last, int(lists[oy, ox]))
+        if not case[5].mask_only:
+            n_contrib = ref.fwd.state.field(so.F_N_CONTRIB).reshape(-1)[in_tile]
+            assert int(n_contrib.max()) == last
+        for i in _rows(ref, "hidden"):
+            assert ref.radii[i] > 0 and not blended[i] and zero_row(i)
+        # the one-pixel tile column and tile row: Gaussians blended there alone, with gradients
+        px, py = np.arange(W * H) % W, np.arange(W * H) // W
+        for cls, coord, edge in (("last_column", px, W - 1), ("last_row", py, H - 1)):
+            assert len(_rows(ref, cls)) == 3
+            for i in _rows(ref, cls):
+                assert blended[i] and (coord[where[i]] == edge).all() and nonzero_row(i, ("dL_drotations",)), (cls, i)
+    else:
+        assert (gx, gy) == (12, 2) and H - 16 * (gy - 1) == 1
+        band = list(er.EMPTY_BAND)
+        ranges = ref.fwd.state.field(so.F_RANGES).reshape(-1, 2)
+        assert len(band) >= 3 and (lists[0, band] == 0).all() and (ranges[band] == 0).all()
+        assert lists[0, band[0] - 1] > 0 and lists[0, band[-1] + 1] > 0
+        assert (tx, ty) == (gx - 2, 0)       # the last full tile of the top tile row
+    # the runs the range scan cuts: not those of equal tile counts, one of a single tile, one of three or more
+    model, equal = er.model_runs(ref)
+    assert sum(a != b for a, b in zip(model[1:8], equal[1:8])) >= 3, (model, equal)
+    lengths = np.diff(model)
+    assert (lengths == 1).any() and lengths.max() >= 3, model
+
+
+def test_tile_rule_sees_a_contribution_lost_from_one_tile():
+    """What the many-tile tests are for: the rows of the two spanning Gaussians are sums over all 21 tiles, and a kernel that loses
+    ONE tile's share of such a row -- the dense tile's, that of the 1 x 16 tile (6, 0), or that of the single pixel that is tile
+    (6, 2) -- is rejected on that row in every gradient class.  The share is the dense float64 gradient of the loss restricted to
+    the tile; it is taken out of a copy of the oracle's row."""
+    import torch
+    ref = er.reference(er.tile_case("t1", "rgb"))
+    inp = ref.inp
+    W, H = inp.image_width, inp.image_height
+    gx = (W + 15) // 16
+    tile_of_pixel = np.arange(H)[:, None] // 16 * gx + np.arange(W)[None] // 16
+    grad_classes = [c for c in ref.classes if c not in er.PIXEL_CLASSES]
+    rows = [_rows(ref, "spanning_front")[0], _rows(ref, "spanning_back")[0]]
+    for tx, ty in (er.DENSE_TILE["t1"], (6, 0), (6, 2)):
+        dL = (ref.dL * (tile_of_pixel == ty * gx + tx)[None]).astype(np.float32)
+        share, _, _ = er._dense(inp, dL, None, torch.float64, True, False)
+        for cls in grad_classes:
+            mutated = ref.oracle[cls].copy()
+            mutated[rows] -= share[cls][rows]
+            r, _ = ref.ratios(cls, mutated, *er.rule(cls, "tiles"))
+            print(f"tile ({tx}, {ty}) lost, {cls}: error / bound {r[rows[0]]:.1f} (front) {r[rows[1]]:.1f} (back)")
+            assert (r[rows] > 1.0).all(), (tx, ty, cls, r[rows])
+            assert (np.delete(r, rows) <= 1.0).all()
