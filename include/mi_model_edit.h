@@ -1,7 +1,4 @@
-/* mi_model_edit.h -- C-ABI of the model cut, in libmi_rast.so.  The library's own header of these four entry points: the public
- * headers in include/ keep their set of functions, and seganygaussians_amd/model_edit.py reads this file with _lib.parse_header and
- * binds what it declares, so the declarations keep to the grammar of include/*.h.  Error codes and
- * mi_rast_last_error() are those of include/mi_rast.h.
+/* mi_model_edit.h -- C-ABI of the model cut, in libmi_rast.so.  Error codes and mi_rast_last_error() are those of mi_rast.h.
  */
 #ifndef MI_MODEL_EDIT_H
 #define MI_MODEL_EDIT_H

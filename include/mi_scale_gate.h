@@ -1,7 +1,4 @@
-/* mi_scale_gate.h -- C-ABI of scale conditioning, in libmi_rast.so.  The library's own header of these three entry points: the
- * public headers in include/ keep their set of functions, and seganygaussians_amd/scale_gate.py reads this file with
- * _lib.parse_header and binds what it declares, so the declarations keep to the grammar of the public headers.  Error
- * codes and mi_rast_last_error() are those of include/mi_rast.h.
+/* mi_scale_gate.h -- C-ABI of scale conditioning, in libmi_rast.so.  Error codes and mi_rast_last_error() are those of mi_rast.h.
  */
 #ifndef MI_SCALE_GATE_H
 #define MI_SCALE_GATE_H

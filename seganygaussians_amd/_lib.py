@@ -112,6 +112,7 @@ MI_MASK_SCORE_MODE = _named("MI_MASK_SCORE_", "sum", "mean", "max")
 MI_CLIP_TILES_LAYOUT = _named("MI_CLIP_TILES_", "crop", "pad_square")
 MI_CLUSTER_METRIC = _named("MI_CLUSTER_", "euclidean", "jaccard")
 MI_SEGMENT_PRE = _named("MI_SEGMENT_PRE_", "none", "l2", "eps")
+MI_SCALE_GATE = _named("MI_SCALE_GATE_", "none", "learned", "fixed")
 
 # the fields of the layout, profile and count tables in the order of their enums: written out, for their case is not the enumerators'
 MI_GEOM_FIELDS = ["depths", "means2D", "conic_opacity", "cov3D", "rgb", "clamped", "tiles_touched",
@@ -120,9 +121,10 @@ MI_IMG_FIELDS = ["final_T", "n_contrib", "ranges", "tile_consumed", "tile_count"
 MI_BIN_FIELDS = ["entries", "scratch", "blend_list"]
 MI_STAGES = ["preprocess", "tile_scan", "emit", "tile_sort", "blend_fwd", "blend_bwd", "geom_bwd"]
 MI_TRAIN_COUNTS = ["clones", "splits", "kept_originals", "kept_clones", "kept_children"]
+MI_EDIT_COUNTS = ["current", "selected", "kept"]
 for _fields, _prefix, _count in ((MI_GEOM_FIELDS, "MI_GEOM_", "MI_GEOM_NFIELDS"), (MI_IMG_FIELDS, "MI_IMG_", "MI_IMG_NFIELDS"),
                                  (MI_BIN_FIELDS, "MI_BIN_", "MI_BIN_NFIELDS"), (MI_STAGES, "MI_STAGE_", "MI_STAGE_COUNT"),
-                                 (MI_TRAIN_COUNTS, "MI_TRAIN_", "MI_TRAIN_NCOUNTS")):
+                                 (MI_TRAIN_COUNTS, "MI_TRAIN_", "MI_TRAIN_NCOUNTS"), (MI_EDIT_COUNTS, "MI_EDIT_", "MI_EDIT_NCOUNTS")):
     if [CONSTANTS.get(_prefix + n.upper()) for n in _fields] != list(range(CONSTANTS[_count])):
         raise MiRastError(f"{_fields} are not the {_count} = {CONSTANTS[_count]} enumerators {_prefix}* of the headers, in order")
 
@@ -146,9 +148,12 @@ def load():
         L = C.CDLL(lib_path)
     except OSError as e:  # e.g. libamdhip64 missing
         raise MiRastError(f"cannot load {lib_path}: {e}") from e
-    for name, (restype, argtypes) in SIGNATURES.items():
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = restype, argtypes
+    try:
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    except AttributeError:     # a library built from other sources than these headers
+        raise MiRastError(f"the HIP library lacks {name} (rebuild it: python -m seganygaussians_amd.build)") from None
     _lib = L
     return L
 

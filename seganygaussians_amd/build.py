@@ -17,7 +17,7 @@ PROF_LIB_PATH = os.path.join(_HERE, "libmi_rast_prof.so")
 SRC_DIR = os.path.join(_HERE, "csrc")
 _INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 # what a library is built from, read off the directories (is_stale() and source_hash() both go by these): every kernel header and
-# host file (one .hip per public header) in csrc/, every public header in include/
+# host file in csrc/, every public header in include/ (csrc/mi_X.hip defines what include/mi_X.h declares: tests/test_abi.py)
 SOURCES = sorted(f for f in os.listdir(SRC_DIR) if f.endswith((".h", ".hip")))
 HEADERS = [os.path.join(_INCLUDE_DIR, h) for h in sorted(os.listdir(_INCLUDE_DIR)) if h.endswith(".h")]
 

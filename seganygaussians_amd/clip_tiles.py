@@ -62,7 +62,7 @@ def clip_tiles(image, masks, size=(224, 224), layout: str = "crop", background=N
     (get_seg_img).  "crop" resizes the ch x cw crop; "pad_square" (pad_img) an L x L plane, L = max(ch, cw), with the crop at column
     (L - cw) // 2 when ch > cw, else at row (L - ch) // 2, the rest bg.  The resize is torchvision's Resize on a tensor,
     F.interpolate(mode='bilinear', align_corners=False, antialias=antialias), in the order of PyTorch's CPU kernels: width pass,
-    then height pass, float32 (include/mi_mask_scales.h states the weights).  Then (r - mean[c]) / std[c] in float32 and one
+    then height pass, float32 (include/mi_clip_tiles.h states the weights).  Then (r - mean[c]) / std[c] in float32 and one
     rounding to `dtype`.  1 <= Sh, Sw <= 512.
 
     "pad_square" stands in for cv2.resize(pad_img(seg_img), (224, 224)) with antialias=False: the same geometry (half-pixel

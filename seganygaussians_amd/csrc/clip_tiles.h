@@ -1,5 +1,5 @@
 // clip_tiles.h -- the CLIP network's input from packed SAM masks and the uint8 image, and the per-pixel mask index map
-// (include/mi_mask_scales.h, its last section; reference: clip_utils/__init__.py:91-191,
+// (include/mi_clip_tiles.h; reference: clip_utils/__init__.py:91-191,
 // clip_utils/sam_utils.py:99-114, :212-225).
 //
 //   tiles     : one workgroup per (mask, band of CT_BAND output rows), one thread per output column (column sets of CT_THREADS).
@@ -17,7 +17,7 @@
 //               have a bit in the word are walked in ascending order and the last that covers a pixel stays.
 #pragma once
 
-#include "../../include/mi_mask_scales.h"
+#include "../../include/mi_clip_tiles.h"
 #include "packed_masks.h"
 
 #include <hip/hip_fp16.h>
@@ -49,7 +49,7 @@ __device__ inline CtAxis ct_axis(int in, int out)
     return a;
 }
 
-// _upsample_bilinear2d_aa's span and triangle weight of output index i, in f32 (include/mi_mask_scales.h states the formulas)
+// _upsample_bilinear2d_aa's span and triangle weight of output index i, in f32 (include/mi_clip_tiles.h states the formulas)
 __device__ inline void ct_aa_span(const CtAxis& a, int i, float& center, int& lo, int& hi)
 {
     center = a.scale * ((float)i + 0.5f);

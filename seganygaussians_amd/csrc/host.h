@@ -1,4 +1,4 @@
-// host.h -- what the host files of the C-ABI library (mi_*.hip, one per public header) share: the calling thread's last error
+// host.h -- what the host files of the C-ABI library (mi_X.hip, one for each public header include/mi_X.h) share: the calling thread's last error
 // (mi_rast_last_error), HIP_TRY, the 256-byte carving of workspaces and state buffers, and the overlap check of a call's byte ranges.
 #pragma once
 

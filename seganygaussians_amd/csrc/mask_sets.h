@@ -1,4 +1,4 @@
-// mask_sets.h -- set operations on bit-packed SAM masks (include/mi_mask_scales.h, its mask-sets section; DESIGN.md section 23;
+// mask_sets.h -- set operations on bit-packed SAM masks (include/mi_mask_sets.h; DESIGN.md section 23;
 // reference: clip_utils/sam_utils.py:123-187 and clip_utils/__init__.py:115, :206, :282, :380).
 //
 //   overlaps     : a GEMM over bits.  One workgroup per (64 x 64 tile of mask pairs on or above the diagonal, slice of the words).
@@ -18,7 +18,7 @@
 //                  masks and visits only those, in ascending order, every K column from the one read.  No atomics.
 #pragma once
 
-#include "../../include/mi_mask_scales.h"
+#include "../../include/mi_mask_sets.h"
 #include "packed_masks.h"
 
 namespace mirast {

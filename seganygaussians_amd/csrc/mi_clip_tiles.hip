@@ -1,7 +1,6 @@
-// mi_clip_tiles.hip -- C-ABI implementation of the CLIP-tiles section of include/mi_mask_scales.h (mi_mask_resize is in
-// mi_mask_scales.hip, beside the erosion whose taps it shares).
+// mi_clip_tiles.hip -- C-ABI implementation of include/mi_clip_tiles.h.
 #include "host.h"
-#include "../../include/mi_mask_scales.h"
+#include "../../include/mi_clip_tiles.h"
 
 #include "clip_tiles.h"   // masked crops resized and normalised for the CLIP network, and the mask index map
 

@@ -1,6 +1,6 @@
-// mi_cluster.hip -- C-ABI implementation of the clustering section of include/mi_segment.h (the second host file of that header).
+// mi_cluster.hip -- C-ABI implementation of include/mi_cluster.h.
 #include "host.h"
-#include "../../include/mi_segment.h"
+#include "../../include/mi_cluster.h"
 
 #include "cluster.h"        // HDBSCAN* on the device: core distances, Boruvka rounds
 #include "cluster_tree.h"   // its host half: from the spanning tree to labels

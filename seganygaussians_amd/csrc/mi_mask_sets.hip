@@ -1,6 +1,6 @@
-// mi_mask_sets.hip -- C-ABI implementation of the mask-sets section of include/mi_mask_scales.h.
+// mi_mask_sets.hip -- C-ABI implementation of include/mi_mask_sets.h.
 #include "host.h"
-#include "../../include/mi_mask_scales.h"
+#include "../../include/mi_mask_sets.h"
 
 #include "mask_sets.h"   // set operations on packed SAM masks: overlaps, boxes, NMS decision, score images
 

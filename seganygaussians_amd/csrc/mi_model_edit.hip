@@ -1,7 +1,7 @@
-// mi_model_edit.hip -- C-ABI implementation of mi_model_edit.h, the model cut.
+// mi_model_edit.hip -- C-ABI implementation of include/mi_model_edit.h, the model cut.
 #include "host.h"
+#include "../../include/mi_model_edit.h"
 
-#include "mi_model_edit.h"
 #include "model_edit.h"   // current rows, selection, the row map; the scan and the gather are row_compact.h's
 
 using namespace mirast;

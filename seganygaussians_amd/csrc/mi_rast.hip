@@ -1,5 +1,5 @@
-// mi_rast.hip -- C-ABI implementation of include/mi_rast.h and host orchestration of the gfx950 rasterizer kernels (the other public
-// headers: mi_knn.hip, mi_contrastive.hip, mi_mask_scales.hip, mi_segment.hip, mi_photometric.hip).  Build: one object per .hip file,
+// mi_rast.hip -- C-ABI implementation of include/mi_rast.h and host orchestration of the gfx950 rasterizer kernels (every other public
+// header include/mi_X.h is implemented by the csrc/mi_X.hip of its name, and by that file alone).  Build: one object per .hip file,
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -munsafe-fp-atomics -fPIC (see seganygaussians_amd/build.py).  No torch, no pybind.
 #include "host.h"
 

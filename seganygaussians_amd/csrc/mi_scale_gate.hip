@@ -1,8 +1,8 @@
-// mi_scale_gate.hip -- C-ABI implementation of mi_scale_gate.h, scale conditioning.  Every entry point
+// mi_scale_gate.hip -- C-ABI implementation of include/mi_scale_gate.h, scale conditioning.  Every entry point
 // checks its arguments, launches ONE kernel on the caller's stream and returns: nothing is allocated, copied or waited for.
 #include "host.h"
+#include "../../include/mi_scale_gate.h"
 
-#include "mi_scale_gate.h"
 #include "scale_gate.h"   // the quantile table, the uniform transform, the gates and their backward
 
 using namespace mirast;

@@ -1,5 +1,6 @@
-// mi_train_step.hip -- C-ABI implementation of the training-step section of include/mi_rast.h (the second host file of that header).
+// mi_train_step.hip -- C-ABI implementation of include/mi_train_step.h.
 #include "host.h"
+#include "../../include/mi_train_step.h"
 
 #include "train_step.h"   // Adam over all groups, densification statistics, densify and prune
 

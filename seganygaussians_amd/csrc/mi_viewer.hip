@@ -1,6 +1,6 @@
-// mi_viewer.hip -- C-ABI implementation of the viewer-frame section of include/mi_segment.h.
+// mi_viewer.hip -- C-ABI implementation of include/mi_viewer.h.
 #include "host.h"
-#include "../../include/mi_segment.h"
+#include "../../include/mi_viewer.h"
 
 #include "viewer.h"        // feature moments for the PCA basis, the fused display frame
 

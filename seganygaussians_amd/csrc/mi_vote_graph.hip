@@ -1,6 +1,6 @@
-// mi_vote_graph.hip -- C-ABI implementation of the vote-graph section of include/mi_segment.h.
+// mi_vote_graph.hip -- C-ABI implementation of include/mi_vote_graph.h.
 #include "host.h"
-#include "../../include/mi_segment.h"
+#include "../../include/mi_vote_graph.h"
 
 #include "packed_masks.h"  // the layout of the eroded masks
 #include "vote_graph.h"    // language-segmentation vote graph: mask features, anchor bits, relevancy

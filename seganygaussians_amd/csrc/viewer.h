@@ -1,5 +1,5 @@
-// viewer.h -- the viewer frame: feature moments for the PCA basis, and the fused display frame (include/mi_segment.h, its last
-// section; reference: saga_gui.py:547-569, 590-599, 645-659, 701-724).
+// viewer.h -- the viewer frame: feature moments for the PCA basis, and the fused display frame (include/mi_viewer.h;
+// DESIGN.md section 25; reference: saga_gui.py:547-569, 590-599, 645-659, 701-724).
 //
 //   moments : a workgroup walks tiles of VIEW_MOM_B rows (tile t, t + gridDim.x, ...).  All 256 threads bring a tile into LDS as
 //             [row][channel] (odd stride, channels padded with zeros to a multiple of 32), 8 lanes per row form |f|^2 and scale
@@ -15,7 +15,7 @@
 //             and the basis sit in LDS as broadcasts; the frame leaves as 3 VEC adjacent floats per lane.
 #pragma once
 
-#include "../../include/mi_segment.h"
+#include "../../include/mi_viewer.h"
 #include "seg_row.h"
 #include <hip/hip_runtime.h>
 #include <stdint.h>

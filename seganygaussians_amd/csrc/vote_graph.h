@@ -1,5 +1,5 @@
-// vote_graph.h -- the language-segmentation vote graph: mask features, anchor bits, CLIP relevancy (include/mi_segment.h, its
-// vote-graph section; reference: prompt_segmenting.ipynb, "Language-driven Segmentation").
+// vote_graph.h -- the language-segmentation vote graph: mask features, anchor bits, CLIP relevancy (include/mi_vote_graph.h;
+// DESIGN.md section 21; reference: prompt_segmenting.ipynb, "Language-driven Segmentation").
 //
 //   resample     : one lane per (channel, working pixel): the bilinear sample of the render in f64, rounded once to f32, into
 //                  Fs [C][h w] (the only O(C h w) buffer).

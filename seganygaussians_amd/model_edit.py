@@ -1,4 +1,4 @@
-"""The cut that ends the segmentation workflow on the MI355X (C entry points: csrc/mi_model_edit.h):
+"""The cut that ends the segmentation workflow on the MI355X (C entry points: include/mi_model_edit.h):
 GaussianModel.segment / roll_back / clear_segment (scene/gaussian_model.py:376-472) and FeatureGaussianModel's
 (scene/gaussian_model_ff.py:257-320), which the GUI's "segment3d", "roll back" and "clear" buttons, the notebooks and render.py call.
 
@@ -15,40 +15,16 @@ there is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch
 
 from . import _lib
 from ._args import f32, no_grad_one_gpu
 from ._ffi import check, stream_ptr
-from .build import SRC_DIR
 
-# The four entry points are declared in the library's own header, not in include/ (whose set of functions is fixed): read with the
-# parser of the public headers, so no signature is written out here either, and bound on first use.
-HEADER = os.path.join(SRC_DIR, "mi_model_edit.h")
-with open(HEADER) as _f:
-    FUNCTIONS, CONSTANTS = _lib.parse_header(_f.read(), "mi_model_edit.h")
-MAX_TENSORS = CONSTANTS["MI_EDIT_MAX_TENSORS"]
-MAX_COLS = CONSTANTS["MI_EDIT_MAX_COLS"]
-COUNTS = ("current", "selected", "kept")
-if [CONSTANTS["MI_EDIT_" + n.upper()] for n in COUNTS] != list(range(CONSTANTS["MI_EDIT_NCOUNTS"])):
-    raise _lib.MiRastError(f"{COUNTS} are not the MI_EDIT_NCOUNTS enumerators of mi_model_edit.h, in order")
-_bound = None
-
-
-def load():
-    """The loaded library with the entry points of mi_model_edit.h bound; a library without them is an error."""
-    global _bound
-    L = _lib.load()
-    if _bound is not L:
-        for name, restype, argtypes in FUNCTIONS:
-            if not hasattr(L, name):
-                raise _lib.MiRastError(f"the HIP library lacks {name} (rebuild it: python -m seganygaussians_amd.build)")
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _bound = L
-    return L
+MAX_TENSORS = _lib.MI_EDIT_MAX_TENSORS
+MAX_COLS = _lib.MI_EDIT_MAX_COLS
+COUNTS = tuple(_lib.MI_EDIT_COUNTS)
 PLAN_LAUNCHES, APPLY_LAUNCHES = 4, 2     # current rows, scan, selection, scan; row map, gather
 EMPTY_MASK_MESSAGE = "Seems like the mask is empty, segmenting the whole point cloud. Please run seg.py first."
 
@@ -108,7 +84,7 @@ class _Plan:
     """plan and counts of one cut: the workspace that carries the row flags to apply, and the three counts."""
 
     def __init__(self, who, level, segment_times, mask, n_rows, dev):
-        L = load()
+        L = _lib.load()
         self.P0, self.n_rows, self.dev = int(level.shape[0]), n_rows, dev
         with torch.cuda.device(dev):
             stream = stream_ptr(dev)
@@ -124,7 +100,7 @@ class _Plan:
 
     def apply(self, level, tensors):
         """New tensors of `kept` rows; level (None: left alone) gets + 1 in every kept original row."""
-        L = load()
+        L = _lib.load()
         dev, kept = self.dev, self.kept
         src = [t.detach() for t in tensors]
         dst = [torch.empty((kept,) + tuple(t.shape[1:]), device=dev, dtype=torch.float32) for t in src]

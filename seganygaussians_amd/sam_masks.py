@@ -93,7 +93,7 @@ def mask_nms(masks, scores, iou_thr=0.7, score_thr=0.1, inner_thr=0.2, **kwargs)
     masks: bool (M, h, w) on the CPU or the scores' GPU, or a PackedSamMasks there; scores: (M,) float32 on a GPU.  Extra keyword
     arguments are ignored, as in the reference.  torch.sort on the device, the overlap kernel through the sort's indices, one
     decision launch, idx[keep]; no (M, M) matrix reaches the host.  The decision is the reference's float32 arithmetic operation
-    for operation (include/mi_mask_scales.h states it), its quirks included: the lower inner test also sees the pair (c-1, c)
+    for operation (include/mi_mask_sets.h states it), its quirks included: the lower inner test also sees the pair (c-1, c)
     (torch.tril(..., diagonal=1) at :164), and of two empty masks the lower-scored one is dropped (0/0 union).
 
     Where this differs from the reference:

@@ -1,4 +1,4 @@
-"""Scale conditioning on the MI355X (C entry points: csrc/mi_scale_gate.h): the two steps every SAGA stage
+"""Scale conditioning on the MI355X (C entry points: include/mi_scale_gate.h): the two steps every SAGA stage
 that takes a 3-D scale goes through -- q_trans, scikit-learn's QuantileTransformer with the uniform output
 (train_contrastive_feature.py:42-62, applied at :228, in the notebook's language loop and in get_similarity_map), and scale_gate,
 Linear(1, 32) + Sigmoid (:83-86, :241), or the fixed 1 / 0 gates of :243-244.
@@ -14,39 +14,16 @@ output_distribution="normal" is not offered: no caller of the reference uses it.
 one GPU; there is no CPU path and neither scikit-learn nor a host round trip."""
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
 from . import _lib
 from ._args import f32
 from ._ffi import check, stream_ptr
-from .build import SRC_DIR
 
-# The three entry points are declared in the library's own header, not in include/ (whose set of functions is fixed): read with the
-# parser of the public headers, so no signature is written out here either, and bound on first use.
-HEADER = os.path.join(SRC_DIR, "mi_scale_gate.h")
-with open(HEADER) as _f:
-    FUNCTIONS, CONSTANTS = _lib.parse_header(_f.read(), "mi_scale_gate.h")
-MAX_QUANTILES = CONSTANTS["MI_SCALE_MAX_QUANTILES"]
-MAX_CHANNELS = CONSTANTS["MI_SCALE_MAX_CHANNELS"]
-_NONE, _LEARNED, _FIXED = (CONSTANTS["MI_SCALE_GATE_" + n] for n in ("NONE", "LEARNED", "FIXED"))
-_bound = None
-
-
-def load():
-    """The loaded library with the entry points of mi_scale_gate.h bound; a library without them is an error."""
-    global _bound
-    L = _lib.load()
-    if _bound is not L:
-        for name, restype, argtypes in FUNCTIONS:
-            if not hasattr(L, name):
-                raise _lib.MiRastError(f"the HIP library lacks {name} (rebuild it: python -m seganygaussians_amd.build)")
-            fn = getattr(L, name)
-            fn.restype, fn.argtypes = restype, argtypes
-        _bound = L
-    return L
+MAX_QUANTILES = _lib.MI_SCALE_MAX_QUANTILES
+MAX_CHANNELS = _lib.MI_SCALE_MAX_CHANNELS
+_NONE, _LEARNED, _FIXED = (_lib.MI_SCALE_GATE[n] for n in ("none", "learned", "fixed"))
 
 
 def _uniform_only(who, distribution):
@@ -103,7 +80,7 @@ class ScaleQuantile:
         if subsample is not None and int(subsample) < n_quantiles:
             raise ValueError(f"{who}: n_quantiles ({n_quantiles}) is greater than subsample ({subsample})")      # as scikit-learn
         data = _gpu_scales(who, "scales", scales)
-        L = load()
+        L = _lib.load()
         dev = data.device
         nq = max(1, min(n_quantiles, N))
         references = torch.from_numpy(np.linspace(0, 1, nq)).to(dev)
@@ -125,7 +102,7 @@ class ScaleQuantile:
         u = torch.empty((n,), device=dev, dtype=torch.float32) if want_u else None
         gates = None if mode == _NONE else torch.empty((n, channels), device=dev, dtype=torch.float32)
         if n:
-            L = load()
+            L = _lib.load()
             with torch.cuda.device(dev):
                 check(L.mi_scale_gate_forward(n, x.data_ptr(), self.n_quantiles_, self.quantiles.data_ptr(), self.references.data_ptr(), mode,
                                               channels, None if weight is None else weight.data_ptr(), None if bias is None else bias.data_ptr(),
@@ -178,7 +155,7 @@ class _ScaleGates(torch.autograd.Function):
         n, channels, dev = int(u.shape[0]), int(b.shape[0]), u.device
         if n == 0:
             return None, None, torch.zeros(ctx.weight_shape, device=dev), torch.zeros_like(b)
-        L = load()
+        L = _lib.load()
         g = g.to(torch.float32).contiguous()
         d_weight, d_bias = torch.empty_like(w), torch.empty_like(b)
         with torch.cuda.device(dev):

@@ -14,7 +14,7 @@ What it restates, by the reference's lines:
                 to every value but -1
 
 The weight tables are computed in float32, one IEEE operation per step (numpy float32 scalars and arrays round every operation
-separately), as include/mi_mask_scales.h states them; tiles_ref64 contracts the exact float32 planes with those float32 weights in
+separately), as include/mi_clip_tiles.h states them; tiles_ref64 contracts the exact float32 planes with those float32 weights in
 float64, so what is left between it and the kernel is the kernel's float32 summation alone."""
 import os
 

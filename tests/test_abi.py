@@ -24,7 +24,7 @@ def test_header_symbols_exported(lib):
     is listed; each is declared in exactly one header, the one _lib.DECLARED lists it under."""
     hdr = "".join(open(h).read() for h in build.HEADERS)
     declared = set(re.findall(r"\b(mi_[a-z_0-9]+)\s*\(", hdr)) - {"mi_rast_resize_fn"}
-    assert len(build.HEADERS) == 7 and len(_lib.ALL_EXPORTS) == len(set(_lib.ALL_EXPORTS))
+    assert len(build.HEADERS) == 15 and len(_lib.ALL_EXPORTS) == len(set(_lib.ALL_EXPORTS))
     assert declared == set(_lib.ALL_EXPORTS), declared ^ set(_lib.ALL_EXPORTS)
     code = {os.path.basename(h): re.sub(r"/\*.*?\*/", " ", open(h).read(), flags=re.S) for h in build.HEADERS}   # comments name functions too
     for name in declared:
@@ -32,6 +32,24 @@ def test_header_symbols_exported(lib):
         assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
         where = [h for h, text in code.items() for _ in re.findall(rf"\b{name}\s*\(", text)]
         assert len(where) == 1 and name in _lib.DECLARED[where[0]], (name, where)
+
+
+def test_one_public_header_per_host_file():
+    """For every csrc/mi_X.hip there is exactly one include/mi_X.h and the reverse, and mi_X.h declares exactly the extern "C" functions
+    that mi_X.hip defines (read off the file: a definition is `type mi_name(...)` followed by its body, not by a semicolon)."""
+    hips = [s for s in build.SOURCES if s.endswith(".hip")]
+    assert {os.path.basename(h)[:-2] for h in build.HEADERS} == {s[:-4] for s in hips} and len(hips) == len(build.HEADERS) == 15
+    assert not [s for s in build.SOURCES if s.startswith("mi_") and s.endswith(".h")]      # no public header is left among the kernels
+    for hip in hips:
+        text = open(os.path.join(build.SRC_DIR, hip)).read()
+        assert 'extern "C"' in text, hip
+        text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+        defined = re.findall(r"^[\w \t*]*?\b(mi_[a-z_0-9]+)\s*\([^;{}]*\)\s*\{", text, flags=re.M)
+        assert sorted(defined) == sorted(_lib.DECLARED[hip[:-4] + ".h"]) and len(defined) == len(set(defined)), hip
+        # its own public header is the first thing it includes after host.h: a definition that disagrees with its declaration does not compile
+        includes = re.findall(r'^#include\s+"([^"]+)"', text, flags=re.M)
+        assert includes[:2] == ["host.h", f"../../include/{hip[:-4]}.h"] or hip == "mi_rast.hip" and includes[0] == "host.h", hip
+    assert '#include "../../include/mi_rast.h"' in open(os.path.join(build.SRC_DIR, "host.h")).read()      # mi_rast.h comes with host.h, for all
 
 
 # ---- the compiler as witness: what a C++ compiler makes of the headers is what _lib read off them ----
@@ -77,7 +95,7 @@ def test_compiler_reads_the_headers_as_lib_does(tmp_path):
     subprocess.check_call([cxx, "-std=c++17", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(tmp_path / "witness")])
     lines = [line.split(" ") for line in subprocess.check_output([str(tmp_path / "witness")], text=True).splitlines()]
     seen = {l[1]: (l[2], l[3]) for l in lines if l[0] == "F"}     # "F name v " for an empty parameter list: l[3] == ""
-    assert len(seen) == len(_lib.SIGNATURES) == 73 and len(lines) == 73 + len(_lib.CONSTANTS)
+    assert len(seen) == len(_lib.SIGNATURES) == 80 and len(lines) == 80 + len(_lib.CONSTANTS)
     for name, (restype, argtypes) in _lib.SIGNATURES.items():
         assert seen[name] == (_CODES[restype], "".join(_CODES[a] for a in argtypes)) and "?" not in "".join(seen[name]), name
     assert {l[1]: int(l[2]) for l in lines if l[0] == "C"} == _lib.CONSTANTS
@@ -109,6 +127,27 @@ def test_lib_binds_in_one_loop_only():
     assert src[hits[0] - 2].strip() == "for name, (restype, argtypes) in SIGNATURES.items():"
     assert not re.search(r"\b(eval|exec)\s*\(", "\n".join(src))
     assert [n for n in vars(_lib) if n.endswith("EXPORTS")] == ["ALL_EXPORTS"]
+    # and _lib is the only binder: no other file of the package assigns a signature or parses a header
+    package = os.path.dirname(_lib.__file__)
+    for root, _, files in os.walk(package):
+        for f in files:
+            if f.endswith(".py") and os.path.join(root, f) != _lib.__file__:
+                assert not re.search(r"\.(argtypes|restype)\b|\bparse_header\b", open(os.path.join(root, f)).read()), os.path.join(root, f)
+
+
+def test_a_library_without_a_declared_symbol_is_refused_by_load(tmp_path, monkeypatch):
+    """What the headers declare and a library does not export is an error when the library is loaded, named, not an AttributeError
+    at the first call."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("c++") or next(p for p in ("/opt/rocm/llvm/bin/clang++", "/opt/rocm/lib/llvm/bin/clang++") if os.path.exists(p))
+    (src := tmp_path / "empty.cpp").write_text('extern "C" int mi_unrelated(void) { return 0; }\n')
+    subprocess.check_call([cxx, "-shared", "-fPIC", str(src), "-o", str(tmp_path / "libempty.so")])
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setenv("MI_RAST_LIB", str(tmp_path / "libempty.so"))
+    with pytest.raises(_lib.MiRastError, match=rf"the HIP library lacks {_lib.ALL_EXPORTS[0]} \(rebuild it: python -m seganygaussians_amd\.build\)"):
+        _lib.load()
+    assert _lib._lib is None
 
 
 # one call per host file of csrc/ that is refused for its arguments before any HIP call (the pointers are never read), and its message
@@ -120,6 +159,14 @@ REFUSED = [
     ("mi_mask_erode", (0, 4, 4, 8, 4, 4, 4096, None), "mask scales: need 1 <= M <= 1024 masks and h, w >= 1"),
     ("mi_segment_scores", (2, 4, 4, 1, 8, 8, None, 0, 1, 8, None), "segment: layout must be MI_SEGMENT_IMAGE or MI_SEGMENT_POINTS"),
     ("mi_photo_loss_forward", (0, 3, 4, 4, 8, 8, 0.2, 3, None, 8, 1 << 20, 8, None), "photometric: need images, planes, H, W >= 1"),
+    ("mi_cluster_core_distances", (2, 100, 32, 8, 10, 8, 8, 1 << 20, None), "cluster: metric must be MI_CLUSTER_EUCLIDEAN or MI_CLUSTER_JACCARD"),
+    ("mi_vote_relevancy", (3, 1025, 1, 1, 4096, 0, 4096, 4096, 1, 4096, None), "vote graph: need N >= 1 rows and 1 <= D <= 1024"),
+    ("mi_view_frame", (0, 4, 8, 8, None, None, 0, None, None, 0.5, 1, 0, 8, None, None, None), "view frame: need N >= 1 and 1 <= C <= 256"),
+    ("mi_mask_nms_keep", (1025, 8, 8, 8, 0.7, 0.1, 0.8, 8, None), "mask nms: need 1 <= M <= 1024 masks"),
+    ("mi_mask_index_map", (1025, 4, 4, 8, 0, 8, None), "clip tiles: need 1 <= M <= 1024 masks and H, W >= 1"),
+    ("mi_train_densify_plan", (0, 1 << 20, 2 << 20, 3 << 20, 4 << 20, 2e-4, 0.005, 5.0, 0.01, 1, 8 << 20, 1 << 20, 16 << 20, None), "densify: need 1 <= P < 2^30 rows"),
+    ("mi_scale_gate_forward", (0, 8, 4, 8, 8, 0, 1, None, None, 0, 8, None, None), "scale gate: need 1 <= n < 2^30 scales"),
+    ("mi_edit_plan", (0, 8, 0, 1, 8, 8, 1 << 20, None), "model edit: need 1 <= P0 < 2^30 rows"),
 ]
 
 
@@ -127,6 +174,8 @@ def test_last_error_is_one_per_thread_for_every_host_file(lib):
     """The host side is one translation unit per public header: what any of them refuses must be what mi_rast_last_error()
     (mi_rast.hip) returns -- one thread-local string for the whole library, not one per file."""
     import threading
+    owners = [next(h for h, names in _lib.DECLARED.items() if name in names) for name, _, _ in REFUSED]
+    assert sorted(owners) == sorted(_lib.DECLARED) and len(owners) == 15      # one refused call of every host file
     for name, args, msg in REFUSED:
         assert getattr(lib, name)(*args) != 0, name
         assert _lib.last_error() == msg, name

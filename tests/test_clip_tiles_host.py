@@ -82,7 +82,7 @@ def test_exports_resolve_and_one_includer():
     build.build_library()
     L = _lib.load()
     names = ["mi_mask_resize", "mi_mask_clip_tiles", "mi_mask_index_map"]
-    assert _lib.DECLARED["mi_mask_scales.h"][-3:] == names          # the section at the header's end
+    assert _lib.DECLARED["mi_clip_tiles.h"] == names[1:] and _lib.DECLARED["mi_mask_scales.h"][-1] == names[0]      # resize: next to its definition
     for name in names:
         assert name in _lib.ALL_EXPORTS
         assert ctypes.cast(getattr(L, name), ctypes.c_void_p).value
@@ -91,7 +91,7 @@ def test_exports_resolve_and_one_includer():
     for name in ("resize_sam_masks", "mask_index_map"):
         assert callable(getattr(sam_masks, name))
     assert clip_tiles.CLIP_MEAN == ref.CLIP_MEAN and clip_tiles.CLIP_STD == ref.CLIP_STD
-    hdr = open(next(h for h in build.HEADERS if os.path.basename(h) == "mi_mask_scales.h")).read()
+    hdr = open(next(h for h in build.HEADERS if os.path.basename(h) == "mi_clip_tiles.h")).read()
     assert f"#define MI_CLIP_TILES_MAX_SIZE {clip_tiles.MAX_SIZE}\n" in hdr and clip_tiles.MAX_SIZE >= 336
     assert f"#define MI_CLIP_TILES_MAX_SIDE {clip_tiles.MAX_SIDE}\n" in hdr and clip_tiles.MAX_SIDE == ref.MAX_SIDE
     includers = [f for f in build.SOURCES if '"clip_tiles.h"' in open(os.path.join(build.SRC_DIR, f)).read()]

@@ -300,10 +300,12 @@ def lib():
 
 
 def test_abi_exported_and_checks_arguments(lib):
-    hdr = open(os.path.join(ROOT, "include", "mi_segment.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "mi_cluster.h")).read()
     declared = set(re.findall(r"\b(mi_cluster_[a-z_0-9]+)\s*\(", hdr))
     assert declared == {"mi_cluster_workspace_bytes", "mi_cluster_core_distances", "mi_cluster_mst", "mi_cluster_mst_rounds",
                         "mi_cluster_labels_host"} <= set(_lib.ALL_EXPORTS)
+    assert _lib.DECLARED["mi_cluster.h"] == ["mi_cluster_workspace_bytes", "mi_cluster_core_distances", "mi_cluster_mst", "mi_cluster_mst_rounds",
+                                             "mi_cluster_labels_host"]
     for name in declared:
         assert ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
     assert {"cluster.h", "cluster_tree.h", "mi_cluster.hip"} <= set(build.SOURCES)

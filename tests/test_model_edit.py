@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import seganygaussians_amd
+from seganygaussians_amd import _lib
 from seganygaussians_amd import model_edit as me
 from tests import model_edit_ref as mr
 
@@ -166,7 +167,7 @@ def test_fixture_sequences_through_the_patched_classes(classes, kind, capsys):
 
 def test_segment_models_is_two_cuts_with_one_host_read(classes, monkeypatch):
     P0 = 1000
-    L = me.load()
+    L = _lib.load()
     calls = {"counts": 0, "plan": 0, "apply": 0}
     for name in calls:
         def wrapped(*args, _name=name, _fn=getattr(L, "mi_edit_" + name)):

@@ -22,7 +22,7 @@ MODULES = ("scene", "scene.gaussian_model", "scene.gaussian_model_ff")
 @pytest.fixture(scope="module")
 def lib():
     build.build_library()
-    return me.load()      # _lib.load() plus the four entry points of csrc/mi_model_edit.h, bound from that header
+    return _lib.load()
 
 
 def test_fixture_holds_what_the_issue_lists():
@@ -139,28 +139,31 @@ def test_entry_points_refuse_before_any_hip_call(lib):
     refused(lib.mi_edit_apply, dict(ap, src=tab([32 << 20, 33 << 20, None]), dst=tab([64 << 20, 8 << 20, None])), "an output overlaps another tensor of the call")
 
 
-def test_the_abi_is_the_librarys_own_header_and_the_public_headers_are_as_they_were(lib):
+def test_the_abi_is_a_public_header_of_its_own_and_lib_alone_binds_it(lib):
     names = ["mi_edit_workspace_bytes", "mi_edit_plan", "mi_edit_counts", "mi_edit_apply"]
-    assert [n for n, _, _ in me.FUNCTIONS] == names and os.path.dirname(me.HEADER) == build.SRC_DIR
-    # the public headers keep their functions and constants: nothing of this feature is declared there, nor known to _lib
-    assert not [n for n in _lib.ALL_EXPORTS if n.startswith("mi_edit_")] and not [n for n in _lib.CONSTANTS if n.startswith("MI_EDIT_")]
-    assert not set(me.CONSTANTS) & set(_lib.CONSTANTS) and "mi_edit" not in open(_lib.__file__).read()
-    assert "mi_edit" not in "".join(open(h).read() for h in build.HEADERS)
+    # a public header like every other: _lib binds what it declares, and the module keeps no binder of its own
+    assert _lib.DECLARED["mi_model_edit.h"] == names and [n for n in _lib.ALL_EXPORTS if n.startswith("mi_edit_")] == names
+    assert {n: v for n, v in _lib.CONSTANTS.items() if n.startswith("MI_EDIT_")} == {
+        "MI_EDIT_MAX_TENSORS": 32, "MI_EDIT_MAX_COLS": 4096, "MI_EDIT_CURRENT": 0, "MI_EDIT_SELECTED": 1, "MI_EDIT_KEPT": 2, "MI_EDIT_NCOUNTS": 3}
+    header = [h for h in build.HEADERS if os.path.basename(h) == "mi_model_edit.h"]
+    assert len(header) == 1 and "mi_model_edit.h" not in build.SOURCES and not [s for s in build.SOURCES if s.startswith("mi_") and s.endswith(".h")]
+    assert not [n for n in ("load", "FUNCTIONS", "HEADER", "CONSTANTS", "_bound") if hasattr(me, n)]
     # bound from the parsed header: int / size_t returns, pointers as void*, and every symbol resolves
-    for name, restype, argtypes in me.FUNCTIONS:
-        fn = getattr(lib, name)
+    for name in names:
+        fn, (restype, argtypes) = getattr(lib, name), _lib.SIGNATURES[name]
         assert C.cast(fn, C.c_void_p).value and fn.restype is restype and list(fn.argtypes) == argtypes, name
     assert lib.mi_edit_workspace_bytes.restype is C.c_size_t and lib.mi_edit_plan.restype is C.c_int
     assert lib.mi_edit_apply.argtypes == [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.c_void_p]
-    hdr = open(me.HEADER).read()
+    hdr = open(header[0]).read()
     assert "#define MI_EDIT_MAX_TENSORS 32\n" in hdr
-    assert (me.MAX_TENSORS, me.MAX_COLS, me.CONSTANTS["MI_EDIT_NCOUNTS"]) == (32, 4096, 3) and me.COUNTS == ("current", "selected", "kept")
+    assert (me.MAX_TENSORS, me.MAX_COLS, _lib.MI_EDIT_NCOUNTS) == (32, 4096, 3) and me.COUNTS == ("current", "selected", "kept")
+    assert me.COUNTS == tuple(_lib.MI_EDIT_COUNTS)      # whose order _lib checks against the enumerators when it is imported
     # a C++ compiler reads the header as the parser does (the declarations are used by mi_model_edit.hip itself: a mismatch with
     # the definitions there would not compile)
     sources = {f: open(os.path.join(build.SRC_DIR, f)).read() for f in build.SOURCES}
-    assert {"model_edit.h", "mi_model_edit.h", "mi_model_edit.hip", "row_compact.h"} <= set(sources)
-    assert [f for f, text in sources.items() if '"mi_model_edit.h"' in text] == ["mi_model_edit.hip"]
+    assert {"model_edit.h", "mi_model_edit.hip", "row_compact.h"} <= set(sources)
+    assert [f for f, text in sources.items() if 'include/mi_model_edit.h"' in text] == ["mi_model_edit.hip"]
     assert [f for f, text in sources.items() if '"model_edit.h"' in text] == ["mi_model_edit.hip"]
     assert [f for f, text in sources.items() if '"train_step.h"' in text] == ["mi_train_step.hip"]
     # the rank, the scan and the gather exist once, in the header both users include

@@ -230,7 +230,7 @@ def test_no_host_synchronisation(golden, tables):
 
 
 def test_a_refused_call_sets_the_last_error(tables):
-    L, sq = sg.load(), tables["gamma"]
+    L, sq = _lib.load(), tables["gamma"]
     x = torch.zeros(4, device=DEV)
     u = torch.empty_like(x)
     args = lambda n, nq: (n, x.data_ptr(), nq, sq.quantiles.data_ptr(), sq.references.data_ptr(), 0, 1, None, None, 0, u.data_ptr(), None, None)

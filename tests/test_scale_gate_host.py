@@ -17,7 +17,7 @@ from tests import scale_gate_ref as sr
 @pytest.fixture(scope="module")
 def lib():
     build.build_library()
-    return sg.load()      # _lib.load() plus the three entry points of csrc/mi_scale_gate.h, bound from that header
+    return _lib.load()
 
 
 @pytest.fixture(scope="module")
@@ -100,23 +100,24 @@ def test_restatement_draws_scikit_learns_subsample(n):
 
 def test_the_abi_is_the_librarys_own_header(lib):
     names = ["mi_scale_quantile_fit", "mi_scale_gate_forward", "mi_scale_gate_backward"]
-    assert [n for n, _, _ in sg.FUNCTIONS] == names and os.path.dirname(sg.HEADER) == build.SRC_DIR
-    assert sg.CONSTANTS == {"MI_SCALE_MAX_QUANTILES": 1024, "MI_SCALE_MAX_CHANNELS": 256, "MI_SCALE_GATE_NONE": 0, "MI_SCALE_GATE_LEARNED": 1,
-                            "MI_SCALE_GATE_FIXED": 2}
-    assert (sg.MAX_QUANTILES, sg.MAX_CHANNELS) == (1024, 256)
-    # nothing of this feature is declared in the public headers, nor known to _lib
-    assert not [n for n in _lib.ALL_EXPORTS if n.startswith("mi_scale_")] and not [n for n in _lib.CONSTANTS if n.startswith("MI_SCALE_")]
-    assert "mi_scale" not in "".join(open(h).read() for h in build.HEADERS) and "mi_scale" not in open(_lib.__file__).read()
-    for name, restype, argtypes in sg.FUNCTIONS:
-        fn = getattr(lib, name)
+    # a public header like every other: _lib binds what it declares, and the module keeps no binder of its own
+    assert _lib.DECLARED["mi_scale_gate.h"] == names and [n for n in _lib.ALL_EXPORTS if n.startswith("mi_scale_")] == names
+    assert {n: v for n, v in _lib.CONSTANTS.items() if n.startswith("MI_SCALE_")} == {
+        "MI_SCALE_MAX_QUANTILES": 1024, "MI_SCALE_MAX_CHANNELS": 256, "MI_SCALE_GATE_NONE": 0, "MI_SCALE_GATE_LEARNED": 1, "MI_SCALE_GATE_FIXED": 2}
+    assert (sg.MAX_QUANTILES, sg.MAX_CHANNELS) == (1024, 256) and (sg._NONE, sg._LEARNED, sg._FIXED) == (0, 1, 2)
+    header = [h for h in build.HEADERS if os.path.basename(h) == "mi_scale_gate.h"]
+    assert len(header) == 1 and "mi_scale_gate.h" not in build.SOURCES and not [s for s in build.SOURCES if s.startswith("mi_") and s.endswith(".h")]
+    assert not [n for n in ("load", "FUNCTIONS", "HEADER", "CONSTANTS", "_bound") if hasattr(sg, n)]
+    for name in names:
+        fn, (restype, argtypes) = getattr(lib, name), _lib.SIGNATURES[name]
         assert C.cast(fn, C.c_void_p).value and fn.restype is restype and list(fn.argtypes) == argtypes, name
     assert lib.mi_scale_quantile_fit.argtypes == [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.mi_scale_gate_forward.argtypes == [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     assert lib.mi_scale_gate_backward.argtypes == [C.c_int, C.c_int] + [C.c_void_p] * 7
     sources = {f: open(os.path.join(build.SRC_DIR, f)).read() for f in build.SOURCES}
-    assert {"scale_gate.h", "mi_scale_gate.h", "mi_scale_gate.hip"} <= set(sources)
-    assert [f for f, text in sources.items() if '"mi_scale_gate.h"' in text] == ["mi_scale_gate.hip"]
+    assert {"scale_gate.h", "mi_scale_gate.hip"} <= set(sources)
+    assert [f for f, text in sources.items() if 'include/mi_scale_gate.h"' in text] == ["mi_scale_gate.hip"]
     assert [f for f, text in sources.items() if '"scale_gate.h"' in text] == ["mi_scale_gate.hip"]
     # what makes the arithmetic reproducible is a build flag, and the kernels say so
     assert "-ffp-contract=off" in build.HIPCC_FLAGS and "-ffp-contract=off" in sources["scale_gate.h"]
@@ -190,7 +191,7 @@ def test_entry_points_refuse_before_any_hip_call(lib):
     for name in ("s", "references", "quantiles"):
         refused(lib.mi_scale_quantile_fit, dict(fit, **{name: None}), "null pointer")
     refused(lib.mi_scale_quantile_fit, dict(fit, quantiles=2 * MB + 8), "an output overlaps another tensor of the call")
-    fwd = dict(n=100, scales=1 * MB, nq=100, quantiles=2 * MB, references=3 * MB, mode=sg.CONSTANTS["MI_SCALE_GATE_LEARNED"], channels=32,
+    fwd = dict(n=100, scales=1 * MB, nq=100, quantiles=2 * MB, references=3 * MB, mode=_lib.MI_SCALE_GATE_LEARNED, channels=32,
                weight=4 * MB, bias=5 * MB, dim=0, u=6 * MB, gates=7 * MB, stream=None)
     refused(lib.mi_scale_gate_forward, dict(fwd, n=0), "need 1 <= n < 2^30 scales")
     refused(lib.mi_scale_gate_forward, dict(fwd, nq=1025), "need 1 <= nq <= 1024 quantiles")

@@ -162,6 +162,7 @@ def test_abi_exported_and_checks_arguments():
     hdr = open(os.path.join(ROOT, "include", "mi_segment.h")).read()
     declared = set(re.findall(r"\b(mi_segment_[a-z_0-9]+)\s*\(", hdr))
     assert declared == {"mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"} <= set(_lib.ALL_EXPORTS)
+    assert _lib.DECLARED["mi_segment.h"] == ["mi_segment_scores", "mi_segment_select", "mi_segment_assign", "mi_segment_assign_block"]
     assert (seg.MAX_CHANNELS, seg.MAX_QUERIES, seg.MAX_CENTERS) == (_lib.MI_SEGMENT_MAX_CHANNELS, _lib.MI_SEGMENT_MAX_QUERIES, _lib.MI_SEGMENT_MAX_CENTERS)
     assert seg.PRE_MODES == _lib.MI_SEGMENT_PRE == {"none": _lib.MI_SEGMENT_PRE_NONE, "l2": _lib.MI_SEGMENT_PRE_L2, "eps": _lib.MI_SEGMENT_PRE_EPS}
     for name in declared:

@@ -219,7 +219,7 @@ def test_abi_exported_and_checks_arguments():
     build.build_library()
     L = _lib.load()
     names = ["mi_view_moments_workspace_bytes", "mi_view_moments_block", "mi_view_moments", "mi_view_frame"]
-    assert [n for n in _lib.DECLARED["mi_segment.h"] if n.startswith("mi_view_")] == names and set(names) <= set(_lib.ALL_EXPORTS)
+    assert _lib.DECLARED["mi_viewer.h"] == names and set(names) <= set(_lib.ALL_EXPORTS)
     for name in names:
         assert ctypes.cast(getattr(L, name), ctypes.c_void_p).value
     assert {"viewer.h", "seg_row.h", "mi_viewer.hip"} <= set(build.SOURCES)
@@ -269,6 +269,6 @@ def test_module_exports():
         seganygaussians_amd.no_such_name
     assert vw.VIEW_MODES == _lib.MI_VIEW_MODES and tuple(vw.VIEW_MODES) == vr.MODES
     assert vw.ViewerFrame._fields == ("frame", "mask", "score")
-    hdr = open(os.path.join(ROOT, "include", "mi_segment.h")).read()
+    hdr = open(os.path.join(ROOT, "include", "mi_viewer.h")).read()
     for name, bit in _lib.MI_VIEW_MODES.items():
         assert f"#define MI_VIEW_{name.upper()} {bit}\n" in hdr

@@ -132,7 +132,7 @@ def test_c_abi_refuses_before_any_launch():
     build.build_library()
     L = _lib.load()
     names = ["mi_vote_mask_features_workspace_bytes", "mi_vote_mask_features", "mi_vote_anchor_bits", "mi_vote_relevancy"]
-    assert [n for n in _lib.DECLARED["mi_segment.h"] if n.startswith("mi_vote_")] == names
+    assert _lib.DECLARED["mi_vote_graph.h"] == names
     for name in names + ["mi_mask_erode_min_sum"]:
         assert name in _lib.ALL_EXPORTS and hasattr(L, name), name
     assert (vg.MAX_ANCHORS, vg.MAX_EMBED_DIM, vg.MAX_PROMPTS) == (32768, 1024, 16) == tuple(_lib.CONSTANTS["MI_VOTE_MAX_" + n] for n in ("ANCHORS", "EMBED_DIM", "PROMPTS"))

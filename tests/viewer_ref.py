@@ -1,4 +1,4 @@
-"""CPU restatement of the viewer frame (include/mi_segment.h, its last section) in float64, and the reference's
+"""CPU restatement of the viewer frame (include/mi_viewer.h) in float64, and the reference's
 own float32 lines transcribed one for one (literal32_*).  The float64 form is the yardstick of tests/test_viewer.py; the literal form
 shows that the reference itself stays inside the yardstick's band (tests/test_viewer_host.py).
 

@@ -11,7 +11,7 @@
                  once, at M = 120, layout "crop", antialias on (the tensor is 3 GB there).
 
 Host clock around work that ends in a device synchronise; median of --reps runs after one warm-up.  alg_MB is the sum over the masks
-of 8 ch ceil(cw / 64) + 3 ch cw + 6 Sh Sw bytes (include/mi_mask_scales.h); `of_8TBs` is the time those bytes would take at 8 TB/s
+of 8 ch ceil(cw / 64) + 3 ch cw + 6 Sh Sw bytes (include/mi_clip_tiles.h); `of_8TBs` is the time those bytes would take at 8 TB/s
 over new_ms.  max_diff is the largest difference between the two results, both float16.  The first line stamps the library build
 measured (mi_rast_version).
 

@@ -11,7 +11,7 @@ pixels, log-uniform: mostly small masks, a few that cover a quarter of the image
                column), .max(0) (:206).
 
 Host clock around work that ends in a device synchronise; median of --reps runs after one warm-up.  `of_8TBs` is the time the
-algorithmic bytes of include/mi_mask_scales.h would take at 8 TB/s over the measured time.  The first line stamps the library build
+algorithmic bytes of include/mi_mask_sets.h would take at 8 TB/s over the measured time.  The first line stamps the library build
 measured (mi_rast_version).
 
     python tools/sam_masks_time.py [--reps 10] [--out profiles/sam_masks_time.txt]"""
