@@ -99,6 +99,16 @@ extern "C" {
                                   other dL_d* pointer may be NULL and is left untouched.  Needs colors_precomp != NULL and a channel count that is a
                                   multiple of 16 (mi_rast_features_only_supported); dL_dcolor equals the default mode's up to the order of the atomic
                                   sums.  seganygaussians_amd/rasterizer.py: enable_features_only_backward() / MI_RAST_FEATURES_ONLY_BACKWARD=1 */
+#define MI_RAST_ANTIALIAS 1024 /* EXTENSION (the Mip-Splatting 2-D filter compensation upstream 3DGS calls `antialiasing`): every projected Gaussian
+                                  gets +0.3 on the diagonal of its 2-D covariance, which adds energy to a splat that is small on screen.  With this
+                                  flag the preprocess stage of mi_rast_forward / mi_rast_mask_forward / mi_rast_lift stores
+                                  w = opacity * sqrt(max(0.000025, det(cov) / det(cov + 0.3 I))) wherever it stores the opacity (float32, every operation
+                                  rounded on its own; csrc/antialias.h); radii, rects, depth keys, num_rendered and the full lists do not change.
+                                  mi_rast_backward MUST be given the flag of its forward (the rule for every flag): dL_dopacity is then the gradient
+                                  of the RAW opacity, and the factor's own gradient reaches dL_dcov3D / dL_dmean3D / dL_dscale / dL_drot by the
+                                  route of the conic gradient.  The *_reuse entries, mi_rast_mask_backward and MI_RAST_BWD_FEATURES_ONLY read the
+                                  stored w and need nothing else.  seganygaussians_amd/rasterizer.py: forward_flags(antialiasing=True),
+                                  enable_antialiasing() / MI_RAST_ANTIALIASING=1 */
 
 /* Replaces std::function<char*(size_t)> (CF/rasterize_points.cu:27-33): must return a device
  * pointer to at least nbytes bytes (256-B aligned), valid until the caller frees it. */

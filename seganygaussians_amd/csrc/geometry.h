@@ -6,6 +6,7 @@
 // contiguous 768-B span, so every fetched line is fully used.
 #pragma once
 
+#include "antialias.h"
 #include "blend_rec.h"
 #include "common.h"
 #include "wave.h"
@@ -45,6 +46,7 @@ __device__ __forceinline__ void computeCov3D(const float3 scale, float mod, cons
 struct Cov2DCtx {
     float3 t;
     float txtz, tytz;
+    float a0, c0;   // the diagonal of cov before the 0.3 px dilation (antialias.h)
     Mat3 T, Vrk, W, cov;
 };
 
@@ -66,6 +68,8 @@ __device__ __forceinline__ void cov2d_common(const float3& mean, const ViewParam
     c.T = m3mul(c.W, J);
     c.Vrk = {{{cov3D[0], cov3D[1], cov3D[2]}, {cov3D[1], cov3D[3], cov3D[4]}, {cov3D[2], cov3D[4], cov3D[5]}}};
     c.cov = m3mul(m3mul(m3transpose(c.T), m3transpose(c.Vrk)), c.T);
+    c.a0 = c.cov.m[0][0];
+    c.c0 = c.cov.m[1][1];
     c.cov.m[0][0] += 0.3f;
     c.cov.m[1][1] += 0.3f;
     c.t = t;
@@ -115,6 +119,8 @@ __device__ __forceinline__ float3 computeColorFromSH(int idx, int deg, const flo
 // `culled_prefiltered` is incremented when prefiltered is set and a point is culled (the reference
 // printf+__trap()s the whole context there; we report an error instead).
 // gfx950 additions (for bin_full.h / bin_lean.h and tile_ranges.h): writes the 32-bit depth sort key (0xFFFFFFFF for culled Gaussians) and accumulates R = sum of tiles_touched of the visible Gaussians.
+// AA (MI_RAST_ANTIALIAS): the opacity stored in conic_opacity and in the packed record is opacity * h (antialias.h); nothing else differs.
+template <bool AA>
 __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
     int P, int D, int M, const float* __restrict__ orig_points, const float* __restrict__ scales,
     const float* __restrict__ rotations, const float* __restrict__ opacities, const float* __restrict__ shs,
@@ -190,6 +196,8 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
         uint2 rmin, rmax;
         getRect(point_image.x, point_image.y, f2i(my_radius), rmin, rmax, vp.grid_x, vp.grid_y);
         if ((rmax.x - rmin.x) * (rmax.y - rmin.y) == 0) break;
+        float aa_w = 0.f;
+        if constexpr (AA) aa_w = opacities[idx] * aa_h(aa_rho(c.a0, cov.y, c.c0, det));
 
         if (!colors_given) {
             const float3 col = computeColorFromSH(idx, D, p_orig, vp, s_sh + threadIdx.x * sh_row, clamped);
@@ -200,7 +208,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
         depths[idx] = p_view.z;
         my_radii = f2i(my_radius);
         points_xy_image[idx] = point_image;
-        conic_opacity[idx] = make_float4(conic.x, conic.y, conic.z, opacities[idx]);
+        conic_opacity[idx] = make_float4(conic.x, conic.y, conic.z, AA ? aa_w : opacities[idx]);
         my_tiles = (rmax.y - rmin.y) * (rmax.x - rmin.x);
         // A Gaussian whose radius converts to <= 0 is "invisible" for every later stage (radii > 0 tests,
         // rasterizer_impl.cu:84, backward.cu:156,369) although tiles_touched is nonzero; keep that.
@@ -213,7 +221,7 @@ __global__ void __launch_bounds__(256) preprocess_fwd_kernel(
             rec.xy = point_image;
             rec.id = my_key;   // the depth bits ride in the record (blend_rec.h: BlendRec)
             rec.pm = (uint32_t)my_radii;
-            rec.co = make_float4(conic.x, conic.y, conic.z, opacities[idx]);
+            rec.co = make_float4(conic.x, conic.y, conic.z, AA ? aa_w : opacities[idx]);
             index_rec[idx] = rec;
         }
     } while (0);
@@ -418,10 +426,14 @@ __device__ __forceinline__ void cov3d_backward(const float3 scale, float mod, co
     dL_drot.w = 2 * r * (dL_dMt.m[0][1] - dL_dMt.m[1][0]) + 2 * x * (dL_dMt.m[2][0] + dL_dMt.m[0][2]) + 2 * y * (dL_dMt.m[1][2] + dL_dMt.m[2][1]) - 4 * z * (dL_dMt.m[1][1] + dL_dMt.m[0][0]);
 }
 
+// AA (MI_RAST_ANTIALIAS, antialias.h): the forward stored w = opacity * h.  h is recomputed by the forward's own expression, the raw
+// opacity is w / h; dL_dopacity = h dL_dw, and dL_dh = opacity dL_dw enters dL_da / dL_db / dL_dc through rho ahead of the push
+// through T, so that it takes the route of the conic gradient.  `pack`: the packed gradients (AA: and the forward's conic_opacity).
+template <bool AA>
 __global__ void __launch_bounds__(256) geometry_bwd_kernel(
     int P, int D, int M, const float* __restrict__ means, const int* __restrict__ radii, const float* __restrict__ shs,
     const uint8_t* __restrict__ clamped, const float* __restrict__ scales, const float* __restrict__ rotations,
-    const float* __restrict__ cov3Ds, ViewParams vp, const float* __restrict__ gpack /*[P,8] from blend_bwd*/,
+    const float* __restrict__ cov3Ds, ViewParams vp, typename GeomBwdPack<AA>::type pack /*[P,8] from blend_bwd*/,
     float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconics, float* __restrict__ dL_dopacity,
     float* __restrict__ dL_dmask, float* __restrict__ dL_dmeans, const float* __restrict__ dL_dcolor,
     float* __restrict__ dL_dcov, float* __restrict__ dL_dsh, float* __restrict__ dL_dscale, float* __restrict__ dL_drot)
@@ -447,13 +459,14 @@ __global__ void __launch_bounds__(256) geometry_bwd_kernel(
 
     // unpack the per-Gaussian record written by the blend backward: {mean2D.x, mean2D.y, conic.x, conic.y,
     // conic.w, opacity, mask, -} -> the reference's dL_dmean2D (P,3), dL_dconic (P,2,2), dL_dopacity, dL_dmask
+    const float* gpack = packed_gradients(pack);
     const float4 g0 = reinterpret_cast<const float4*>(gpack)[2 * idx];
     const float4 g1 = reinterpret_cast<const float4*>(gpack)[2 * idx + 1];
     dL_dmean2D[3 * idx + 0] = g0.x;
     dL_dmean2D[3 * idx + 1] = g0.y;
     dL_dmean2D[3 * idx + 2] = 0.f;  // never written by the reference either (backward.cu:541-542): stays the glue's zero
     reinterpret_cast<float4*>(dL_dconics)[idx] = make_float4(g0.z, g0.w, 0.f, g1.x);
-    dL_dopacity[idx] = g1.y;
+    if constexpr (!AA) dL_dopacity[idx] = g1.y;
     if (dL_dmask) dL_dmask[idx] = g1.z;
 
     // ---- computeCov2DCUDA, backward.cu:144-274
@@ -480,10 +493,27 @@ __global__ void __launch_bounds__(256) geometry_bwd_kernel(
     float dL_da = 0, dL_db = 0, dL_dc = 0;
     const float denom2inv = 1.0f / ((denom * denom) + 0.0000001f);
     float dcov[6];
+    float aa_rho_v = 0.f, aa_h_v = 1.f;
+    if constexpr (AA) {
+        aa_rho_v = aa_rho(c.a0, b, c.c0, denom);
+        aa_h_v = aa_h(aa_rho_v);
+        dL_dopacity[idx] = aa_h_v * g1.y;
+    }
     if (denom2inv != 0) {
         dL_da = denom2inv * (-cc * cc * dL_dconic.x + 2 * b * cc * dL_dconic.y + (denom - a * cc) * dL_dconic.z);
         dL_dc = denom2inv * (-a * a * dL_dconic.z + 2 * a * b * dL_dconic.y + (denom - a * cc) * dL_dconic.x);
         dL_db = denom2inv * 2 * (b * cc * dL_dconic.x - (denom + 2 * b * b) * dL_dconic.y + a * b * dL_dconic.z);
+        if constexpr (AA) {
+            if (aa_rho_v > AA_RHO_FLOOR) {
+                const float opacity = pack.conic_opacity[idx].w / aa_h_v;
+                const float g_rho = (opacity * g1.y) / (2.0f * aa_h_v);
+                const float det0 = c.a0 * c.c0 - b * b;
+                const float det1sq_inv = 1.0f / (denom * denom);
+                dL_da += g_rho * ((c.c0 * denom - det0 * cc) * det1sq_inv);
+                dL_dc += g_rho * ((c.a0 * denom - det0 * a) * det1sq_inv);
+                dL_db += g_rho * ((-2.0f * b * (denom - det0)) * det1sq_inv);
+            }
+        }
         dcov[0] = (T.m[0][0] * T.m[0][0] * dL_da + T.m[0][0] * T.m[1][0] * dL_db + T.m[1][0] * T.m[1][0] * dL_dc);
         dcov[3] = (T.m[0][1] * T.m[0][1] * dL_da + T.m[0][1] * T.m[1][1] * dL_db + T.m[1][1] * T.m[1][1] * dL_dc);
         dcov[5] = (T.m[0][2] * T.m[0][2] * dL_da + T.m[0][2] * T.m[1][2] * dL_db + T.m[1][2] * T.m[1][2] * dL_dc);

@@ -340,6 +340,7 @@ struct Call {
     uint32_t longest_run;   // of the XCD runs of tiles (a forward reads it at the ev2 wait, a reuse is handed it; 0: unknown): the forward blend's grid
     uint32_t ntiles() const { return vp.grid_x * vp.grid_y; }
     size_t HW() const { return (size_t)vp.W * vp.H; }   // floats of one image plane
+    bool antialias() const { return (flags & MI_RAST_ANTIALIAS) != 0; }   // the two geometry kernels: antialias.h
     bool xexp() const { return (flags & MI_RAST_FAST_EXP) == 0; }   // the device library's expf (common.h gauss_exp), the default
     // the wave-per-quadrant forward kernels: common.h ExpMode
     int exp_mode() const { return (flags & MI_RAST_FAST_EXP) ? EXP_FAST : (flags & MI_RAST_EXACT_EXP) ? EXP_EXACT : EXP_HYBRID; }
@@ -398,11 +399,13 @@ int preprocess_stage(const Call& c, const FrontArgs& a, const BinPlan& bp)
         // SH colours: the workgroup's coefficient rows are staged in LDS (geometry.h), 256 rows of 3 M + 4 floats
         const size_t sh_lds = a.colors_given ? 0 : (size_t)256 * (3 * (size_t)a.M + 4) * sizeof(float);
         if (sh_lds > 64 * 1024) return fail(MI_RAST_ERR_INVALID, "too many SH coefficients per Gaussian (at most 16: degree 3)");
-        hipLaunchKernelGGL(preprocess_fwd_kernel, dim3((P + 255) / 256), dim3(256), sh_lds, c.stream, P, a.D, a.M, a.means3D, a.scales,
-                           a.rotations, a.opacities, a.shs, c.geom.clamped, a.cov3D_precomp, a.colors_given, c.vp, a.radii,
-                           c.geom.means2D, c.geom.depths, c.geom.cov3D, c.geom.rgb, c.geom.conic_opacity, c.geom.tiles_touched,
-                           c.geom.depth_key, c.geom.index_rec, c.img.num_rendered, a.prefiltered, c.geom.cull_counter, c.geom.band_bits,
-                           bp.lean_band_h, bp.lean_nbands, c.img.tile_cursor, (uint32_t)ntiles);
+        with_bool(c.antialias(), [&](auto aa) {
+            hipLaunchKernelGGL(preprocess_fwd_kernel<decltype(aa)::value>, dim3((P + 255) / 256), dim3(256), sh_lds, c.stream, P, a.D, a.M, a.means3D,
+                               a.scales, a.rotations, a.opacities, a.shs, c.geom.clamped, a.cov3D_precomp, a.colors_given, c.vp, a.radii,
+                               c.geom.means2D, c.geom.depths, c.geom.cov3D, c.geom.rgb, c.geom.conic_opacity, c.geom.tiles_touched,
+                               c.geom.depth_key, c.geom.index_rec, c.img.num_rendered, a.prefiltered, c.geom.cull_counter,
+                               c.geom.band_bits, bp.lean_band_h, bp.lean_nbands, c.img.tile_cursor, (uint32_t)ntiles);
+        });
     }
     STAGE_CHECK(c, "preprocess");
     if (a.prefiltered) {
@@ -1096,9 +1099,15 @@ int mi_rast_backward(int P, int D, int M, int channels, int R, const float* back
     const float* cov3D_ptr = (cov3D_precomp != nullptr) ? cov3D_precomp : geom.cov3D;  // rasterizer_impl.cu:411
     {
         StageTimer t(c.stream, MI_STAGE_GEOM_BWD);
-        hipLaunchKernelGGL(geometry_bwd_kernel, dim3((P + 255) / 256), dim3(256), 0, c.stream, P, D, M, means3D, radii, shs,
-                           geom.clamped, scales, rotations, cov3D_ptr, c.vp, geom.bwd_pack, dL_dmean2D, dL_dconic, dL_dopacity,
-                           dL_dmask, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+        // (antialiased forward: the kernel also reads the w = opacity * h that forward stored, antialias.h)
+        with_bool(c.antialias(), [&](auto aa) {
+            typename GeomBwdPack<decltype(aa)::value>::type pack;
+            if constexpr (decltype(aa)::value) pack = GeomBwdPackAA{geom.bwd_pack, geom.conic_opacity};
+            else pack = geom.bwd_pack;
+            hipLaunchKernelGGL(geometry_bwd_kernel<decltype(aa)::value>, dim3((P + 255) / 256), dim3(256), 0, c.stream, P, D, M, means3D, radii, shs,
+                               geom.clamped, scales, rotations, cov3D_ptr, c.vp, pack, dL_dmean2D, dL_dconic, dL_dopacity,
+                               dL_dmask, dL_dmean3D, dL_dcolor, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
+        });
     }
     STAGE_CHECK(c, "preprocess backward");
     return MI_RAST_OK;

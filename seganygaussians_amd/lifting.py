@@ -81,7 +81,7 @@ def lift_scores(scores, means3D, opacities, *, scales=None, rotations=None, cov3
         votes = out
     if P == 0:
         empty = torch.empty(0, dtype=torch.uint8, device=dev)
-        st = state or LiftState(0, torch.zeros(0, dtype=torch.int32, device=dev), empty, empty, empty, W, H, int(_opts.flags))
+        st = state or LiftState(0, torch.zeros(0, dtype=torch.int32, device=dev), empty, empty, empty, W, H, _opts.call_flags())
         return (votes, st) if return_state else votes
     L = _lib.load()
     s_c = contig(s.detach())
@@ -101,12 +101,12 @@ def lift_scores(scores, means3D, opacities, *, scales=None, rotations=None, cov3
             geom.cb, None, binning.cb, None, img.cb, None, P, K, W, H, dev_ptr(m3_c, "means3D", dev), dev_ptr(op_c, "opacities", dev),
             dev_ptr(sc_c, "scales", dev), float(scale_modifier), dev_ptr(rot_c, "rotations", dev), dev_ptr(cov_c, "cov3D_precomp", dev),
             dev_ptr(vm_c, "viewmatrix", dev), dev_ptr(pm_c, "projmatrix", dev), float(tanfovx), float(tanfovy),
-            int(bool(prefiltered)), dev_ptr(s_c, "scores", dev), votes.data_ptr(), radii.data_ptr(), 0, int(_opts.flags),
+            int(bool(prefiltered)), dev_ptr(s_c, "scores", dev), votes.data_ptr(), radii.data_ptr(), 0, _opts.call_flags(),
             stream_ptr(dev), C.byref(n))
     check(rc)
     if not return_state:
         return votes
-    return votes, LiftState(n.value, radii, geom.tensor, binning.tensor, img.tensor, W, H, int(_opts.flags))
+    return votes, LiftState(n.value, radii, geom.tensor, binning.tensor, img.tensor, W, H, _opts.call_flags())
 
 
 def state_of_forward(num_rendered, radii, geomBuffer, binningBuffer, imageBuffer, image_width, image_height, flags=None):
@@ -115,7 +115,7 @@ def state_of_forward(num_rendered, radii, geomBuffer, binningBuffer, imageBuffer
     forward left on its geometry buffer)."""
     if flags is None:
         notes = geomBuffer.__dict__.get("mi_notes")
-        flags = notes.flags if notes is not None else _opts.flags
+        flags = notes.flags if notes is not None else _opts.call_flags()
     return LiftState(int(num_rendered), radii, geomBuffer, binningBuffer, imageBuffer, int(image_width), int(image_height), int(flags))
 
 

@@ -78,13 +78,36 @@ class _CallOptions(threading.local):
         self.features_ready = None   # torch.cuda.Event, kept alive until the forward that consumes it has returned
         self.grad_mode = True        # torch.is_grad_enabled() of the CALLER (autograd switches it off inside Function.forward)
 
+    def call_flags(self):
+        """The flags of the next forward: this thread's forward_flags() plus the process-wide switches (enable_antialiasing)."""
+        return int(self.flags) | (_lib.MI_RAST_ANTIALIAS if _antialiasing else 0)
+
 
 _opts = _CallOptions()
+
+# ---- antialiased render mode (EXTENSION, include/mi_rast.h: MI_RAST_ANTIALIAS) ---------------------------------------------------
+# The opacity of every Gaussian is scaled by sqrt(det(cov2D) / det(cov2D + 0.3 I)): the Mip-Splatting compensation of the 0.3 px
+# screen filter, upstream 3DGS's `antialiasing` switch.  GaussianRasterizationSettings keeps the reference's fields, so the mode is
+# a flag: forward_flags(antialiasing=True) per block and thread, or process-wide -- enable_antialiasing() / MI_RAST_ANTIALIASING=1
+# in the environment, for unchanged reference scripts -- which ORs the bit into every forward of the three drop-in packages (and
+# of lifting.lift_scores).  The backward gets the bit through ForwardNotes like every flag.
+_antialiasing = os.environ.get("MI_RAST_ANTIALIASING", "") not in ("", "0")
+
+
+def enable_antialiasing(on=True):
+    """Process-wide opt-in to the antialiased render mode (see above); returns the previous setting."""
+    global _antialiasing
+    prev, _antialiasing = _antialiasing, bool(on)
+    return prev
+
+
+def antialiasing_enabled():
+    return _antialiasing
 
 
 @contextlib.contextmanager
 def forward_flags(full_lists=None, f32_blend=None, no_cull=None, fast_exp=None, verify_lists=None, tile_fwd=None, exact_exp=None,
-                  equal_runs=None):
+                  equal_runs=None, antialiasing=None):
     """Within the block, forwards of this thread run with the given modes: `full_lists` materialises the reference's
     point_list / full-list positions (parity tests), `f32_blend` / `tile_fwd` select the f32 FMA-chain / tile-batched forwards for 32/64
     channels (comparison kernels of the PROFILING build only -- MI_RAST_LIB=libmi_rast_prof.so; the product library refuses them with
@@ -93,12 +116,16 @@ def forward_flags(full_lists=None, f32_blend=None, no_cull=None, fast_exp=None, 
     alpha >= 1/255 decisions differ from the reference's); `verify_lists` (debugging aid) checks that the count and emit passes of the
     lean lists agree slot by slot; `exact_exp` makes the forward blend call expf for every pair (product default: the hybrid form of
     csrc/common.h -- same decisions, alpha to 1e-6): alpha / T / n_contrib / final_T are then bit-identical to a build of the
-    reference's kernels; `equal_runs` (A/B aid) keeps the blend kernels' XCD runs at equal tile counts instead of equal modelled work.  The flags of a
+    reference's kernels; `equal_runs` (A/B aid) keeps the blend kernels' XCD runs at equal tile counts instead of equal modelled work;
+    `antialiasing` scales every opacity by sqrt(det(cov2D) / det(cov2D + 0.3 I)) (include/mi_rast.h: MI_RAST_ANTIALIAS; the process-wide
+    switch enable_antialiasing() / MI_RAST_ANTIALIASING=1 is ORed in after these flags, so antialiasing=False cannot switch the mode
+    off for a block while that switch is on: call enable_antialiasing(False)).  The flags of a
     forward are remembered with its buffers and handed to its backward."""
     prev = _opts.flags
     for bit, v in ((_lib.MI_RAST_FULL_LISTS, full_lists), (_lib.MI_RAST_F32_BLEND, f32_blend), (_lib.MI_RAST_NO_CULL, no_cull),
                    (_lib.MI_RAST_FAST_EXP, fast_exp), (_lib.MI_RAST_VERIFY_LISTS, verify_lists),
-                   (_lib.MI_RAST_TILE_FWD, tile_fwd), (_lib.MI_RAST_EXACT_EXP, exact_exp), (_lib.MI_RAST_EQUAL_RUNS, equal_runs)):
+                   (_lib.MI_RAST_TILE_FWD, tile_fwd), (_lib.MI_RAST_EXACT_EXP, exact_exp), (_lib.MI_RAST_EQUAL_RUNS, equal_runs),
+                   (_lib.MI_RAST_ANTIALIAS, antialiasing)):
         if v is not None:
             _opts.flags = (_opts.flags | bit) if v else (_opts.flags & ~bit)
     try:
@@ -211,7 +238,7 @@ def rasterize_gaussians_native(channels, with_mask_depth, background, means3D, c
                                   viewmatrix, projmatrix, campos, mask)]
         bg_c, m3_c, sh_c, col_c, op_c, sc_c, rot_c, cov_c, vm_c, pm_c, cp_c, mk_c = t
         n = C.c_int(0)
-        flags = int(_opts.flags)
+        flags = _opts.call_flags()
         grad_colors = None
         if prezero and (P <= H * W or prezero == "always"):
             grad_colors = torch.empty((P, channels), dtype=torch.float32, device=dev)
@@ -425,6 +452,7 @@ def rasterize_mask_gaussians_native(means3D, opacity, mask, scales, rotations, s
         t = [contig(x) for x in (means3D, opacity, mask, scales, rotations, cov3D_precomp, viewmatrix, projmatrix)]
         m3_c, op_c, mk_c, sc_c, rot_c, cov_c, vm_c, pm_c = t
         n = C.c_int(0)
+        mask_flags = _opts.call_flags()
         with torch.cuda.device(dev):
             rc = L.mi_rast_mask_forward(
                 geom.cb, None, binning.cb, None, img.cb, None, P, W, H, dev_ptr(m3_c, "means3D", dev),
@@ -432,10 +460,10 @@ def rasterize_mask_gaussians_native(means3D, opacity, mask, scales, rotations, s
                 float(scale_modifier), dev_ptr(rot_c, "rotations", dev), dev_ptr(cov_c, "cov3D_precomp", dev),
                 dev_ptr(vm_c, "viewmatrix", dev), dev_ptr(pm_c, "projmatrix", dev), float(tan_fovx),
                 float(tan_fovy), int(bool(prefiltered)), out_mask.data_ptr(), radii.data_ptr(), int(bool(debug)),
-                int(_opts.flags), stream_ptr(dev), C.byref(n))
+                mask_flags, stream_ptr(dev), C.byref(n))
         check(rc)
         rendered = n.value
-        geom.tensor.mi_notes = ForwardNotes(_opts.flags)
+        geom.tensor.mi_notes = ForwardNotes(mask_flags)
     else:
         out_mask = torch.zeros((1, H, W), dtype=torch.float32, device=dev)
     return rendered, out_mask, radii, geom.tensor, binning.tensor, img.tensor
